@@ -7,7 +7,16 @@ resident batch of synthetic docs:d#view@u requests (16M per GPU by default).  Th
 request with no data-path collective: every rank holds the whole snapshot (the 1B-tuple arena is
 17.2 GiB of a 288 GB HBM3E) and checks its own batch ("weak" scaling).  Rank 0 prints one JSON line.
 
-Extras on the same line:
+A plain run does what the headline figure needs: it generates the graph, uploads the snapshot, warms
+up, times the K steps and prints the line (metric, value, unit, ms_per_step, config, the cheap
+detail fields).  --dump-outputs DIR also writes the decisions of the last timed step as
+DIR/allowed.npy (float32, request order; batches over 8M requests as a fixed seeded sample of 4M of
+them, whose request indexes are in DIR/allowed_index.npy as float64).  The graph and the batch are
+seeded, so the same arguments give the same inputs in every run.  The plain run's snapshot carries
+no string table (only the string_form leg needs one); its arena equals the --full run's up to the
+subject-id values, and the decisions and the step time are the same.
+
+Extras on the same line, with --full only (each is a run of its own next to the timed steps):
   roofline      SURVEY.md 8(d) algorithmic bytes of the dominant kernel (the tier-0 check kernel)
                 per launch -- B_check(q) = 14 + sum over the BFS rows (8 + 4 deg), priced by the
                 oracle's BFS-count mode on a 1 % sample of the batch and scaled -- divided by the
@@ -105,7 +114,17 @@ def parse():
     ap.add_argument("--e2e-only", action="store_true", help="time only the end-to-end leg (profiling runs)")
     ap.add_argument("--string-steps", type=int, default=3,
                     help="N = 1: batches timed through keto_check_batch with named requests (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs: roofline / work counters, device_row_ids, end_to_end, string_form, "
+                         "cpu_baseline, ref_sql, parity (and --e2e-only, --check-parity); off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the decisions of the last timed step to DIR/allowed.npy (float32)")
     a = ap.parse_args()
+    if not a.full:
+        if a.e2e_only or a.check_parity:
+            ap.error("--e2e-only and --check-parity are extra legs: add --full")
+        a.no_work = True
+        a.e2e_steps = a.string_steps = 0
     from tools.hostcpu import host_cores
     a.host = host_cores()
     if a.threads is None:
@@ -267,6 +286,23 @@ def string_form(g, u, snap, q, a):
             "host_resolution": host, "_out": pa.copy()}
 
 
+DUMP_FULL_MAX = 8 * 1024 * 1024        # decisions written whole up to this many (float32: 32 MiB)
+DUMP_SAMPLE = 4 * 1024 * 1024          # else this many of them, drawn with DUMP_SEED
+DUMP_SEED = 20240
+
+
+def dump_outputs(path, decisions, rank, world):
+    """--dump-outputs: what the timed path left in the caller's decision buffer after the last timed
+    step (1 = allowed, 0 = denied), as float32 in request order; every rank writes its own batch."""
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    if len(decisions) > DUMP_FULL_MAX:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(len(decisions), DUMP_SAMPLE, replace=False))
+        np.save(os.path.join(path, f"allowed_index{tag}.npy"), idx.astype(np.float64))
+        decisions = decisions[idx]
+    np.save(os.path.join(path, f"allowed{tag}.npy"), decisions.astype(np.float32))
+
+
 def rusage():
     import resource
     r = resource.getrusage(resource.RUSAGE_SELF)
@@ -275,12 +311,31 @@ def rusage():
 
 def main():
     a = parse()
-    import torch
-    import torch.distributed as dist
-
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+
+    # the generator (host threads of tools/synth.cpp, no GPU) runs while torch loads and opens the device
+    import threading
+    from tools import synth
+
+    params = synth.scaled(synth.POWERLAW_1B, a.scale) if a.scale != 1.0 else dict(synth.POWERLAW_1B)
+    log(f"rank {rank}/{world}: generating the graph (scale {a.scale})")
+    made = {}
+
+    def generate():
+        t0 = time.time()
+        try:
+            made["g"] = synth.SynthGraph(params, threads=a.threads)
+        except BaseException as e:
+            made["error"] = e
+        made["s"] = time.time() - t0
+
+    gen = threading.Thread(target=generate, daemon=True)
+    gen.start()
+    import torch
+    import torch.distributed as dist
+
     # one rank per GPU over RCCL; KETO_BENCH_BACKEND=gloo (rehearsal: several ranks sharing the
     # GPUs of a smaller box, the rank's device = LOCAL_RANK modulo the devices) -- never the driver's run
     backend = os.environ.get("KETO_BENCH_BACKEND", "nccl")
@@ -295,13 +350,10 @@ def main():
         torch.cuda.set_device(0)
     dev = torch.cuda.current_device()
 
-    from tools import synth
-
-    params = synth.scaled(synth.POWERLAW_1B, a.scale) if a.scale != 1.0 else dict(synth.POWERLAW_1B)
-    log(f"rank {rank}/{world}: generating the graph (scale {a.scale})")
-    t0 = time.time()
-    g = synth.SynthGraph(params, threads=a.threads)
-    t_gen = time.time() - t0
+    gen.join()
+    if "error" in made:
+        raise made["error"]
+    g, t_gen = made["g"], made["s"]
     log(f"rank {rank}: {g.n_edges} tuples, {g.n_rows} rows; building + uploading the snapshot")
     t0 = time.time()
     migrate = a.partitioned and a.part_mode == "migrate"
@@ -366,7 +418,7 @@ def main():
     if not migrate and not a.partitioned and unified is not None:
         strf = string_form(g, unified, snap, q_gen, a)
     rows_dev = None
-    if not a.partitioned and not migrate and a.steps > 0:
+    if a.full and not a.partitioned and not migrate and a.steps > 0:
         # the same batch resident in HBM by row id (what the resolution produces): keto_check_batch_rows_device,
         # the row id -> handle translation inside the timed region (detail only; value times the handle form)
         d_rows = torch.from_numpy(np.ascontiguousarray(q).view(np.uint8)).to(f"cuda:{dev}")
@@ -423,6 +475,8 @@ def main():
     work = None
     allowed_rate = float(d_out.float().mean().item())
     gpu_out = d_out.cpu().numpy()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, gpu_out, rank, world)
     cpu = None
     parity = None
     ref_sql = None
@@ -532,8 +586,8 @@ def main():
         line = {
             "metric": "checks/sec (whole node) on 1B-tuple graph, max-depth 5; % of HBM roofline",
             "value": round(value, 1), "unit": "checks/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "warmup": a.warmup, "full": a.full, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
             "config": {"workload": "powerlaw-acl-1B (BASELINE config #4) on one GPU per rank, " +
                                    ("migrating partition (every row on one part, searches move between parts as "
                                     f"records, {a.hot_mb} MB of replicated hot rows per part)" if migrate else

@@ -17,7 +17,7 @@ step smoke
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -30 $out/smoke.log; exit 1; }
 tail -2 $out/smoke.log
 step bench
-timeout -k 10 400 python -u bench.py "$@" > $out/bench.log 2>&1 || { tail -30 $out/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full "$@" > $out/bench.log 2>&1 || { tail -30 $out/bench.log; exit 1; }
 tail -1 $out/bench.log
 fi
 [ -n "$SKIP_PROFILE" ] && { step done; exit 0; }

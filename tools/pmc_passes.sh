@@ -11,7 +11,7 @@ while read -r grp; do
   [ -z "$grp" ] && continue
   i=$((i+1))
   echo "== $(date +%T) pass $i: $grp"
-  timeout -s KILL 240 rocprofv3 --pmc $grp --output-format csv -d $out/p$i -o p -- python -u bench.py --no-cpu-baseline --no-work "$@" > $out/p$i.log 2>&1 || { tail -20 $out/p$i.log; exit 1; }
+  timeout -s KILL 240 rocprofv3 --pmc $grp --output-format csv -d $out/p$i -o p -- python -u bench.py --full --no-cpu-baseline --no-work "$@" > $out/p$i.log 2>&1 || { tail -20 $out/p$i.log; exit 1; }
 done <<'GROUPS'
 FETCH_SIZE
 WRITE_SIZE
