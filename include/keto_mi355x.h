@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define KETO_ABI_VERSION 6
+#define KETO_ABI_VERSION 7
 /* The largest arena one snapshot (a replica) or one partition part takes on a device: handles are
  * 32-bit; below 2^31 a count of 16-byte units (subject-set targets, and the root rows of the first
  * 32 GiB), above it a count of 32-, 64- or 128-byte units of the root rows past 32 GiB (arenas past
@@ -532,7 +532,8 @@ int keto_check_steps_device(keto_snapshot* s, const keto_check_ids* d_reqs, uint
 
 /* Batched BuildTree.  The arena owns all trees; free it with keto_tree_arena_free.  Its node array
  * lives in page-locked host memory from a process-wide pool (blocks are recycled by later arenas;
- * up to 1 GiB of idle blocks is kept), so keto_tree_proto_all_device uploads it in one DMA. */
+ * up to 1 GiB of idle blocks is kept), so keto_tree_proto_all_device and
+ * keto_tree_json_all_device upload it in one DMA. */
 int keto_expand_batch(keto_snapshot* s, const keto_expand_req* reqs, uint32_t n, int32_t global_max_depth,
                       keto_tree_arena** out);
 /* Same with pre-resolved roots: roots[i] bit31 set -> subject set (bits 0..30 = row id), else a
@@ -575,6 +576,15 @@ int64_t keto_tree_proto_all(const keto_snapshot* s, const keto_tree_arena* a, ui
  * state); a pinned (hipHostMalloc'd) buf takes one DMA, a pageable one two pinned bounce chunks. */
 int64_t keto_tree_proto_all_device(keto_snapshot* s, const keto_tree_arena* a, uint8_t* buf, uint64_t cap,
                                    uint64_t* offsets);
+/* keto_tree_json_all encoded on the GPU the same way (the REST Expand response bodies, batched): the
+ * same text and offsets -- keto_tree_json's text for a tree, "null" for a nil tree, empty for
+ * KETO_EXPAND_NOT_FOUND / KETO_EXPAND_UNDECIDED roots, no NUL terminator.  offsets[n+1] is always
+ * written; buf only when cap >= the returned total (call with buf = NULL to size it; unlike
+ * keto_tree_json_all, nothing is kept between the sizing and the filling call).  Buffers as
+ * keto_tree_proto_all_device: a pinned buf takes one DMA, a pageable one the two bounce chunks.
+ * Fails like keto_tree_proto_all_device on a host-only snapshot (device = -1). */
+int64_t keto_tree_json_all_device(keto_snapshot* s, const keto_tree_arena* a, char* buf, uint64_t cap,
+                                  uint64_t* offsets);
 
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,

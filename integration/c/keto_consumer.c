@@ -453,6 +453,17 @@ static int print_trees(keto_snapshot* snap, keto_tree_arena* ar, uint32_t m, int
     if (an < 0) fail("keto_tree_json_all", (int)an);
     char* all = (char*)xrealloc(NULL, (size_t)an + 1);
     if (keto_tree_json_all(snap, ar, all, (uint64_t)an, offs) != an) return 6;
+    /* the same text encoded on the GPU: sizes, offsets and bytes equal the host encoder's */
+    {
+        uint64_t* doffs = (uint64_t*)xrealloc(NULL, (m + 1) * sizeof(uint64_t));
+        const int64_t dn = keto_tree_json_all_device(snap, ar, NULL, 0, doffs);
+        if (dn < 0) fail("keto_tree_json_all_device", (int)dn);
+        char* dall = (char*)xrealloc(NULL, (size_t)dn + 1);
+        if (dn != an || keto_tree_json_all_device(snap, ar, dall, (uint64_t)dn, doffs) != dn) return 6;
+        if (memcmp(doffs, offs, (m + 1) * sizeof(uint64_t)) != 0 || memcmp(dall, all, (size_t)an) != 0) return 6;
+        free(dall);
+        free(doffs);
+    }
     for (uint32_t k = 0; k < m; ++k) {
         const int s = keto_tree_status(ar, k);
         const int64_t jn = keto_tree_json(snap, ar, k, NULL, 0);

@@ -622,6 +622,73 @@ func (s *Snapshot) expandWith(subs []relationtuple.Subject, depths []int,
 	return trees, errs, nil
 }
 
+// JSONAllDevice = BuildTree + Tree.MarshalJSON (internal/expand/tree.go:85-163) for many roots, the
+// text encoded on the GPU (keto_tree_json_all_device): bodies[i] is the REST Expand response body of
+// root i (internal/expand/handler.go:77-91; "null" for a nil tree), nil where errs[i] is ErrNotFound /
+// ErrUndecided.  The bodies share one Go buffer that the encoder fills: it is passed as a plain
+// argument, not inside a struct, which the cgo rules allow for the length of the call, and saves a
+// copy of the whole text out of C memory.
+func (s *Snapshot) JSONAllDevice(subs []relationtuple.Subject, depths []int, globalMax int) ([][]byte, []error, error) {
+	n := len(subs)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	if len(depths) != n {
+		return nil, nil, fmt.Errorf("gpu: %d roots, %d depths", n, len(depths))
+	}
+	var m cmem
+	defer m.free()
+	total := 0
+	for _, sub := range subs {
+		total += subjectLen(sub)
+	}
+	m.strings(total)
+	cr := (*C.keto_expand_req)(m.alloc((n + 1) * int(C.sizeof_keto_expand_req)))
+	cs := unsafe.Slice(cr, n)
+	for i, sub := range subs {
+		cs[i] = C.keto_expand_req{subject: m.subject(sub), max_depth: C.int32_t(depths[i])}
+	}
+	var a *C.keto_tree_arena
+	if rc := C.keto_expand_batch(s.h, cr, C.uint32_t(n), C.int32_t(globalMax), &a); rc != C.KETO_OK {
+		return nil, nil, lastErr(rc)
+	}
+	defer C.keto_tree_arena_free(a)
+	offs := (*C.uint64_t)(m.alloc((n + 1) * 8))
+	// sizing call, then the filling call; a write in between may lengthen a string, so the fill is
+	// retried while it reports a larger total
+	size := C.keto_tree_json_all_device(s.h, a, nil, 0, offs)
+	if size < 0 {
+		return nil, nil, lastErr(C.int(size))
+	}
+	var text []byte
+	for {
+		buf := make([]byte, int(size)+1)
+		got := C.keto_tree_json_all_device(s.h, a, (*C.char)(unsafe.Pointer(&buf[0])), C.uint64_t(size), offs)
+		if got < 0 {
+			return nil, nil, lastErr(C.int(got))
+		}
+		if got <= size {
+			text = buf[:int(got)]
+			break
+		}
+		size = got
+	}
+	off := unsafe.Slice(offs, n+1)
+	bodies := make([][]byte, n)
+	errs := make([]error, n)
+	for i := 0; i < n; i++ {
+		switch C.keto_tree_status(a, C.uint32_t(i)) {
+		case C.KETO_EXPAND_NOT_FOUND:
+			errs[i] = ErrNotFound
+		case C.KETO_EXPAND_UNDECIDED:
+			errs[i] = ErrUndecided
+		default:
+			bodies[i] = text[int(off[i]):int(off[i+1]):int(off[i+1])]
+		}
+	}
+	return bodies, errs, nil
+}
+
 // subjects resolves subject references of arena a (keto_tree_node.subject) to Subjects with one
 // keto_subject_fields sizing call and one filling call; a reference's strings never change, so the
 // pair agrees even if a write lands in between (the fill is retried on a larger total regardless).

@@ -38,7 +38,7 @@ def _stale(target, deps):
 
 
 def build(verbose=False, force=False):
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "parallel.hpp"), os.path.join(CSRC, "snapshot.hpp"), os.path.join(CSRC, "capi_internal.hpp"),
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "parallel.hpp"), os.path.join(CSRC, "snapshot.hpp"), os.path.join(CSRC, "capi_internal.hpp"), os.path.join(CSRC, "json_runs.hpp"),
                                                         os.path.join(HERE, "..", "include", "keto_mi355x.h"), os.path.abspath(__file__)]
     if not force and not _stale(OUT, deps):
         return OUT

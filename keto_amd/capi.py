@@ -16,7 +16,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KETO_LIB") or os.path.join(HERE, "libketo_mi355x.so")   # KETO_LIB: tuning builds
 
-KETO_ABI_VERSION = 6          # include/keto_mi355x.h KETO_ABI_VERSION: load() refuses any other library
+KETO_ABI_VERSION = 7          # include/keto_mi355x.h KETO_ABI_VERSION: load() refuses any other library
 KETO_OK = 0
 E_REBUILD = -6
 CHECK_OK, CHECK_UNKNOWN_NAMESPACE, CHECK_UNDECIDED = 0, 1, 2
@@ -37,7 +37,7 @@ EXPORTS = [
     "keto_check_steps_device", "keto_snapshot_part_stats", "keto_snapshot_apply", "keto_snapshot_version",
     "keto_snapshot_upload_part_mode", "keto_snapshot_part_stats_mode", "keto_part_stubs", "keto_part_filters",
     "keto_part_close", "keto_part_closure_done", "keto_mig_begin", "keto_mig_round", "keto_device_copy", "keto_device_memory", "keto_snapshot_upload_part_migrate",
-    "keto_tree_proto_all_device", "keto_tree_json_all", "keto_subject_fields",
+    "keto_tree_proto_all_device", "keto_tree_json_all", "keto_tree_json_all_device", "keto_subject_fields",
     "keto_comm_id", "keto_comm_init", "keto_comm_free", "keto_check_batch_sharded", "keto_check_batch_routed",
     "keto_check_batch_routed_packed",
     "keto_comm_close_filters", "keto_comm_init_local", "keto_snapshot_clone", "keto_check_batch_packed",
@@ -97,7 +97,7 @@ def pack_requests(reqs):
     off = 0
     for i, (ns, obj, rel, sub, depth) in enumerate(reqs):
         fields = [ns, obj, rel] + ([sub[1]] if sub[0] == "id" else list(sub[1:4]))
-        enc = [f.encode() for f in fields]
+        enc = [f if isinstance(f, bytes) else f.encode() for f in fields]
         out[i]["off"] = off
         out[i]["len"][:len(enc)] = [len(x) for x in enc]
         out[i]["kind"] = 0 if sub[0] == "id" else 1
@@ -192,6 +192,7 @@ def load():
     lib.keto_tree_proto_all.restype = C.c_int64
     lib.keto_tree_proto_all_device.restype = C.c_int64
     lib.keto_tree_json_all.restype = C.c_int64
+    lib.keto_tree_json_all_device.restype = C.c_int64
     lib.keto_subject_string.restype = C.c_int64
     lib.keto_subject_fields.restype = C.c_int64
     lib.keto_route_work_bytes.restype = C.c_uint64
@@ -262,8 +263,8 @@ class _Keep:
     def __init__(self):
         self.items = []
 
-    def s(self, x: str) -> KStr:
-        b = x.encode()
+    def s(self, x) -> KStr:
+        b = x if isinstance(x, bytes) else x.encode()       # bytes: as they are (any byte sequence)
         self.items.append(b)
         return KStr(b, len(b))
 
@@ -669,6 +670,27 @@ class Snapshot:
             self.lib.keto_tree_arena_free(a)
         return status, offs, blob, t1 - t0, t_enc
 
+    def expand_batch_ids_json(self, roots: np.ndarray, depths: np.ndarray, global_max_depth=5, device=False):
+        """Pre-resolved roots -> every tree's JSON text in one buffer (keto_tree_json_all, or
+        keto_tree_json_all_device).  Returns (status[n], offsets[n+1] into the blob, blob, expand seconds,
+        encode seconds)."""
+        import time
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        depths = np.ascontiguousarray(depths, dtype=np.int32)
+        n = len(roots)
+        a = C.c_void_p()
+        t0 = time.perf_counter()
+        _check(self.lib.keto_expand_batch_ids(self.h, roots.ctypes.data_as(C.c_void_p),
+                                              depths.ctypes.data_as(C.c_void_p), C.c_uint32(n),
+                                              C.c_int32(global_max_depth), C.byref(a)))
+        t1 = time.perf_counter()
+        try:
+            offs, blob, t_enc = self._json_all_raw(a, n, device=device)
+            status = np.array([self.lib.keto_tree_status(a, C.c_uint32(i)) for i in range(n)], dtype=np.int32)
+        finally:
+            self.lib.keto_tree_arena_free(a)
+        return status, offs, blob, t1 - t0, t_enc
+
     def _proto_all(self, a, n, device=False):
         """(offsets[n+1], blob, seconds of the sizing + filling calls, as a caller pays them) of
         keto_tree_proto_all[_device] (the host encoder keeps a sizing call's encodings for the fill)."""
@@ -685,15 +707,25 @@ class Snapshot:
         assert got == total
         return offs, blob[:total].tobytes(), dt
 
-    def _json_all(self, a, n):
-        """Every tree's JSON text from keto_tree_json_all ("null" for nil trees, "" for errors)."""
+    def _json_all_raw(self, a, n, device=False):
+        """(offsets[n+1], blob, seconds of the sizing + filling calls) of keto_tree_json_all[_device]."""
+        import time
+        fn = self.lib.keto_tree_json_all_device if device else self.lib.keto_tree_json_all
         offs = np.zeros(n + 1, dtype=np.uint64)
-        total = self.lib.keto_tree_json_all(self.h, a, None, C.c_uint64(0), offs.ctypes.data_as(C.c_void_p))
+        t0 = time.perf_counter()
+        total = fn(self.h, a, None, C.c_uint64(0), offs.ctypes.data_as(C.c_void_p))
         _check(min(0, total))
-        blob = C.create_string_buffer(max(1, total))
-        got = self.lib.keto_tree_json_all(self.h, a, blob, C.c_uint64(total), offs.ctypes.data_as(C.c_void_p))
+        blob = np.empty(max(1, total), dtype=np.uint8)
+        got = fn(self.h, a, blob.ctypes.data_as(C.c_void_p), C.c_uint64(total), offs.ctypes.data_as(C.c_void_p))
+        dt = time.perf_counter() - t0
         _check(min(0, got))
-        raw = blob.raw[:total]
+        assert got == total
+        return offs, blob[:total].tobytes(), dt
+
+    def _json_all(self, a, n, device=False):
+        """Every tree's JSON text from keto_tree_json_all, or keto_tree_json_all_device ("null" for nil
+        trees, "" for errors)."""
+        offs, raw, _ = self._json_all_raw(a, n, device=device)
         return [raw[int(offs[i]):int(offs[i + 1])].decode() for i in range(n)]
 
     def subject_fields(self, refs, arena=None):
@@ -749,8 +781,8 @@ class Snapshot:
                      json_all=False, via_fields=False):
         """reqs: list of (subject, max_depth). Returns list of (status, json_or_None[, nodes][, proto]);
         proto_all = "host" / "device": also every tree's bytes from keto_tree_proto_all[_device]
-        (returned as (list, per-tree bytes list)); json_all: also every tree's JSON text from
-        keto_tree_json_all (returned as (list, per-tree text list)); via_fields: also each tree rebuilt
+        (returned as (list, per-tree bytes list)); json_all (True / "host" / "device"): also every tree's
+        JSON text from keto_tree_json_all[_device] (returned as (list, per-tree text list)); via_fields: also each tree rebuilt
         from its nodes and keto_subject_fields (the Go shim's path), as a dict."""
         keep = _Keep()
         n = len(reqs)
@@ -801,7 +833,7 @@ class Snapshot:
                 offs, blob, _ = self._proto_all(a, n, device=proto_all == "device")
                 return out, [blob[int(offs[i]):int(offs[i + 1])] for i in range(n)]
             if json_all:
-                return out, self._json_all(a, n)
+                return out, self._json_all(a, n, device=json_all == "device")
         finally:
             self.lib.keto_tree_arena_free(a)
         return out

@@ -1163,6 +1163,42 @@ int64_t keto_tree_proto_all_device(keto_snapshot* h, const keto_tree_arena* a, u
     });
 }
 
+int64_t keto_tree_json_all_device(keto_snapshot* h, const keto_tree_arena* a, char* buf, uint64_t cap,
+                                  uint64_t* offsets) {
+    return guarded([&]() -> int64_t {
+        if (!h || !a || !offsets) throw Error{KETO_E_INVALID, "NULL argument"};
+        std::shared_lock<RwGate> rlk(h->s->rw);    // strings / row keys (before S.mu)
+        const uint32_t n = (uint32_t)a->r.status.size();
+        // the nodes of the trees as in keto_tree_proto_all_device; nil trees ("null") marked
+        std::vector<uint64_t> toff(n + 1, 0);
+        std::vector<uint8_t> nil(n, 0);
+        bool all = true;
+        for (uint32_t i = 0; i < n; ++i) {
+            const int st = a->r.status[i];
+            all &= st == KETO_EXPAND_TREE || a->r.offset[i] == a->r.offset[i + 1];
+            nil[i] = st != KETO_EXPAND_TREE && st != KETO_EXPAND_NOT_FOUND && st != KETO_EXPAND_UNDECIDED;
+        }
+        std::vector<keto_tree_node> sel;
+        const keto_tree_node* nodes = a->r.nodes.data();
+        uint64_t n_nodes = a->r.nodes.size();
+        if (all) {
+            for (uint32_t i = 0; i <= n; ++i) toff[i] = a->r.offset[i];
+            n_nodes = std::min<uint64_t>(n_nodes, toff[n]);
+        } else {
+            for (uint32_t i = 0; i < n; ++i) {
+                toff[i] = sel.size();
+                if (a->r.status[i] == KETO_EXPAND_TREE)
+                    sel.insert(sel.end(), a->r.nodes.begin() + a->r.offset[i], a->r.nodes.begin() + a->r.offset[i + 1]);
+            }
+            toff[n] = sel.size();
+            nodes = sel.data();
+            n_nodes = sel.size();
+        }
+        return (int64_t)device_tree_json(*h->s, nodes, n_nodes, toff.data(), nil.data(), n, a->ov_base, a->ov_keys,
+                                         a->extra_base, a->extra, reinterpret_cast<uint8_t*>(buf), cap, offsets);
+    });
+}
+
 int64_t keto_subject_fields(const keto_snapshot* h, const keto_tree_arena* a, const uint32_t* subjects, uint64_t n,
                             char* buf, uint64_t cap, uint32_t* lens_out) {
     return guarded([&]() -> int64_t {

@@ -16,6 +16,10 @@
 //   3. per node: its header length; one exclusive scan over all nodes gives every node's byte
 //      offset, the trees' offsets included;
 //   4. per node (parallel): write the header and the subject's strings.
+//
+// keto_tree_json_all_device (the "json_" kernels below) encodes the same trees as Tree.MarshalJSON
+// text from the same tables, with the same leaf-run serial pass: it finds where every union closes
+// instead of how large it is.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -26,6 +30,7 @@
 #include <cstring>
 #include <vector>
 
+#include "json_runs.hpp"
 #include "parallel.hpp"
 #include "snapshot.hpp"
 
@@ -300,6 +305,264 @@ __global__ void __launch_bounds__(256) proto_tree_offsets(const uint64_t* __rest
     out[t] = toff[t] < n_nodes ? pos[toff[t]] : total;
 }
 
+// ---- Tree.MarshalJSON text (keto_tree_json_all_device): tree_json / subject_json / json_escape of
+// capi.cpp, byte for byte.  A node's text is not contiguous -- a union with children opens before
+// its first child and closes behind its last -- so the output is laid out as, for every node k in
+// pre-order: [the closes of the unions whose subtree ends right before k, innermost first]
+// [the "null"s of the nil trees in front of a tree root] [a comma unless k is a first child or a
+// root] [k's own text: everything for a leaf or a childless union, the open text for a union with
+// children].  One exclusive scan of these per-node byte counts places everything.
+
+// json_escape's classification of the sequence starting at s[i]: the bytes it consumes (1 for an
+// invalid one) and the bytes it emits; raw = copy the consumed bytes unchanged
+struct Esc {
+    uint32_t take, emit;
+    bool raw;
+    uint32_t cp;                  // the code point of an escaped multi-byte sequence, 0xFFFD if invalid
+};
+__device__ inline Esc esc_at(const uint8_t* s, uint32_t i, uint32_t l) {
+    const uint8_t c = s[i];
+    if (c < 0x80) {
+        if (c == '"' || c == '\\' || c == '\n' || c == '\r' || c == '\t') return Esc{1, 2, false, c};
+        if (c < 0x20 || c == '<' || c == '>' || c == '&') return Esc{1, 6, false, c};
+        return Esc{1, 1, true, c};
+    }
+    const uint32_t len = (c >> 5) == 6 ? 2 : (c >> 4) == 14 ? 3 : (c >> 3) == 30 ? 4 : 0;
+    bool ok = len != 0 && (uint64_t)i + len <= l;
+    uint32_t cp = 0;
+    if (ok) {
+        cp = c & (0x7Fu >> len);
+        for (uint32_t k = 1; k < len; ++k) {
+            const uint8_t cc = s[i + k];
+            if ((cc >> 6) != 2) {
+                ok = false;
+                break;
+            }
+            cp = (cp << 6) | (cc & 0x3Fu);
+        }
+        if (ok && ((len == 2 && cp < 0x80) || (len == 3 && cp < 0x800) || (len == 4 && (cp < 0x10000 || cp > 0x10FFFF)) ||
+                   (cp >= 0xD800 && cp <= 0xDFFF)))
+            ok = false;
+    }
+    if (!ok) return Esc{1, 6, false, 0xFFFDu};
+    if (cp == 0x2028 || cp == 0x2029) return Esc{len, 6, false, cp};
+    return Esc{len, len, true, cp};
+}
+// bytes of json_escape's output for a string of the tables, the quotes included
+__device__ inline uint64_t esc_len(const StrTab* t, uint32_t i) {
+    const uint32_t l = slen_of(t, i);
+    uint64_t n = 2;
+    if (!l) return n;
+    const uint8_t* s = t->bytes + t->off[i];
+    for (uint32_t c = 0; c < l;) {
+        const Esc e = esc_at(s, c, l);
+        n += e.emit;
+        c += e.take;
+    }
+    return n;
+}
+__device__ inline uint8_t* put_lit(uint8_t* p, const char* s, uint32_t n) {
+    for (uint32_t c = 0; c < n; ++c) p[c] = (uint8_t)s[c];
+    return p + n;
+}
+#define PUT_LIT(p, s) put_lit((p), (s), (uint32_t)sizeof(s) - 1)
+__device__ inline uint8_t* put_esc(uint8_t* p, const StrTab* t, uint32_t i) {
+    const uint32_t l = slen_of(t, i);
+    *p++ = '"';
+    if (l) {
+        const uint8_t* s = t->bytes + t->off[i];
+        for (uint32_t c = 0; c < l;) {
+            const Esc e = esc_at(s, c, l);
+            if (e.raw) {
+                for (uint32_t k = 0; k < e.take; ++k) *p++ = s[c + k];
+            } else if (e.emit == 2) {
+                *p++ = '\\';
+                *p++ = e.cp == '\n' ? 'n' : e.cp == '\r' ? 'r' : e.cp == '\t' ? 't' : (uint8_t)e.cp;
+            } else {
+                *p++ = '\\';
+                *p++ = 'u';
+                for (int sh = 12; sh >= 0; sh -= 4) {
+                    const uint32_t h = (e.cp >> sh) & 15u;
+                    *p++ = (uint8_t)(h < 10 ? '0' + h : 'a' + (h - 10));
+                }
+            }
+            c += e.take;
+        }
+    }
+    *p++ = '"';
+    return p;
+}
+
+// subject_json: ,"subject_id":"..."} | ,"subject_set":{"namespace":"...","object":"...","relation":"..."}}
+__device__ inline uint64_t subject_json_len(const Sub& s) {
+    if (!s.set) return 14 + esc_len(s.t[0], s.i[0]) + 1;
+    return 28 + esc_len(s.t[0], s.i[0]) + 10 + esc_len(s.t[1], s.i[1]) + 12 + esc_len(s.t[2], s.i[2]) + 2;
+}
+__device__ inline uint8_t* put_subject_json(uint8_t* p, const Sub& s) {
+    if (!s.set) {
+        p = PUT_LIT(p, ",\"subject_id\":");
+        p = put_esc(p, s.t[0], s.i[0]);
+    } else {
+        p = PUT_LIT(p, ",\"subject_set\":{\"namespace\":");
+        p = put_esc(p, s.t[0], s.i[0]);
+        p = PUT_LIT(p, ",\"object\":");
+        p = put_esc(p, s.t[1], s.i[1]);
+        p = PUT_LIT(p, ",\"relation\":");
+        p = put_esc(p, s.t[2], s.i[2]);
+        *p++ = '}';
+    }
+    *p++ = '}';
+    return p;
+}
+__device__ inline bool json_open_union(const keto_tree_node& x) {     // a union with children: closes later
+    return (x.info & 0x80000000u) == 0 && (x.info & 0x7FFFFFFFu) != 0;
+}
+
+// per node: own = the text at the node's place (all of a leaf's or a childless union's, the open
+// text of a union with children), clen = the close text a union with children writes behind its
+// last child; uni as in proto_slen
+__global__ void __launch_bounds__(256) json_own(const keto_tree_node* __restrict__ nd, uint64_t n, Tables T,
+                                                uint64_t* __restrict__ own, uint64_t* __restrict__ clen,
+                                                int64_t* __restrict__ uni) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const keto_tree_node x = nd[k];
+    const uint64_t sl = subject_json_len(subject_of(T, x.subject));
+    const bool leaf = (x.info & 0x80000000u) != 0;
+    if (json_open_union(x)) {
+        own[k] = 28;                                      // {"type":"union","children":[
+        clen[k] = 1 + sl;                                 // ] and the subject
+    } else {
+        own[k] = (leaf ? 14 : 15) + sl;                   // {"type":"leaf" | {"type":"union"
+        clen[k] = 0;
+    }
+    uni[k] = leaf ? -1 : (int64_t)k;
+}
+
+// pre[k] = the "null" bytes in front of tree root k, -1 for every other node; pre[n_nodes] = the
+// ones behind the last node.  run[t] = the "null" bytes of the node-less trees right before tree t
+// (t = n_trees: at the end).
+__global__ void __launch_bounds__(256) json_roots(const uint64_t* __restrict__ toff, uint32_t n_trees,
+                                                  const uint64_t* __restrict__ run, uint64_t n_nodes,
+                                                  int64_t* __restrict__ pre) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_trees && toff[t] < toff[t + 1]) pre[toff[t]] = (int64_t)run[t];
+    if (t == n_trees) pre[n_nodes] = (int64_t)run[n_trees];
+}
+
+// one lane per tree, reverse pre-order with leaf runs as single steps (proto_sizes): where every
+// union with children closes.  Stack entries (2 words in the tree's slice of `st`): a finished
+// union {ST_UNION, end of its subtree} or a run of leaves {first, end}.  Union u closes right before
+// node cend[u] = the end of its last child; the unions that close there are reached innermost
+// first, so close_at[cend[u]] before u's add is u's byte offset in that group (coff[u]).  A lane
+// writes close_at in (b, e] only: no two trees share an entry.  A node list cut short closes what
+// is open at its end, as tree_json does.
+__global__ void __launch_bounds__(256) json_closes(const keto_tree_node* __restrict__ nd,
+                                                   const uint64_t* __restrict__ toff, uint32_t n_trees,
+                                                   const int64_t* __restrict__ last_union,
+                                                   const uint64_t* __restrict__ clen, uint64_t* __restrict__ close_at,
+                                                   uint64_t* __restrict__ cend, uint64_t* __restrict__ coff,
+                                                   uint64_t* __restrict__ st) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_trees) return;
+    const uint64_t b = toff[t], e = toff[t + 1];
+    uint64_t* const stack = st + 2 * b;
+    uint64_t sp = 0;
+    uint64_t k = e;
+    while (k > b) {
+        --k;
+        if (nd[k].info & 0x80000000u) {                   // the run of leaves ending at k
+            const int64_t u = last_union[k];
+            const uint64_t first = (u < 0 || (uint64_t)u < b) ? b : (uint64_t)u + 1;
+            stack[2 * sp] = first;
+            stack[2 * sp + 1] = k + 1;
+            ++sp;
+            k = first;
+            continue;
+        }
+        uint32_t need = nd[k].info & 0x7FFFFFFFu;
+        const bool open = need != 0;
+        uint64_t end = k + 1;
+        while (need > 0 && sp > 0) {
+            uint64_t* top = stack + 2 * (sp - 1);
+            if (top[0] == ST_UNION) {
+                end = top[1];
+                --need;
+                --sp;
+                continue;
+            }
+            const uint64_t m = top[1] - top[0], take = m < need ? m : need;   // the first `take` leaves
+            need -= (uint32_t)take;
+            top[0] += take;
+            end = top[0];
+            if (top[0] == top[1]) --sp;
+        }
+        if (open) {
+            const uint64_t at = close_at[end];
+            coff[k] = at;
+            cend[k] = end;
+            close_at[end] = at + clen[k];
+        }
+        stack[2 * sp] = ST_UNION;
+        stack[2 * sp + 1] = end;
+        ++sp;
+    }
+}
+
+// the bytes laid out at node k (k = n_nodes: behind the last node)
+__global__ void __launch_bounds__(256) json_term(const keto_tree_node* __restrict__ nd, uint64_t n,
+                                                 const uint64_t* __restrict__ own, const uint64_t* __restrict__ close_at,
+                                                 const int64_t* __restrict__ pre, uint64_t* __restrict__ term) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > n) return;
+    const int64_t pr = pre[k];
+    uint64_t z = close_at[k] + (pr < 0 ? 0 : (uint64_t)pr);
+    if (k < n) z += own[k] + ((pr < 0 && k > 0 && !json_open_union(nd[k - 1])) ? 1 : 0);
+    term[k] = z;
+}
+
+__global__ void __launch_bounds__(256) json_write(const keto_tree_node* __restrict__ nd, uint64_t n, Tables T,
+                                                  const uint64_t* __restrict__ close_at, const int64_t* __restrict__ pre,
+                                                  const uint64_t* __restrict__ cend, const uint64_t* __restrict__ coff,
+                                                  const uint64_t* __restrict__ pos, uint8_t* __restrict__ out) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const keto_tree_node x = nd[k];
+    const int64_t pr = pre[k];
+    uint8_t* p = out + pos[k] + close_at[k] + (pr < 0 ? 0 : (uint64_t)pr);
+    if (pr < 0 && k > 0 && !json_open_union(nd[k - 1])) *p++ = ',';
+    const Sub s = subject_of(T, x.subject);
+    if (json_open_union(x)) {
+        PUT_LIT(p, "{\"type\":\"union\",\"children\":[");
+        p = out + pos[cend[k]] + coff[k];
+        *p++ = ']';
+    } else if (x.info & 0x80000000u) {
+        p = PUT_LIT(p, "{\"type\":\"leaf\"");
+    } else {
+        p = PUT_LIT(p, "{\"type\":\"union\"");
+    }
+    put_subject_json(p, s);
+}
+
+// per tree: its offset; a nil tree's "null".  A tree without nodes (nil, error) lies run[t] bytes
+// into the "null"s in front of the next root.
+__global__ void __launch_bounds__(256) json_trees(const uint64_t* __restrict__ toff, uint32_t n_trees,
+                                                  const uint64_t* __restrict__ run, const uint8_t* __restrict__ nil,
+                                                  const uint64_t* __restrict__ close_at, const uint64_t* __restrict__ pos,
+                                                  uint64_t n_nodes, uint8_t* __restrict__ out,
+                                                  uint64_t* __restrict__ offs) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n_trees) return;
+    if (t == n_trees) {
+        if (offs) offs[t] = pos[n_nodes + 1];
+        return;
+    }
+    const uint64_t b = toff[t];
+    const uint64_t at = pos[b] + close_at[b] + run[t];
+    if (offs) offs[t] = at;
+    if (out && nil[t]) PUT_LIT(out + at, "null");
+}
+
 // a string table on the device from host strings (its buffers are reused by the next upload)
 struct DevStrs {
     PBuf b_bytes, b_off;
@@ -335,6 +598,7 @@ struct DevStrs {
 struct ProtoWork {
     DevStrs ex;
     PBuf ons, oobj, orel, nodes, toff, slen, size, st, root, hdr, pos, out, to, tmp, tmp3, lw, lp, uni, lu;
+    PBuf jown, jclen, jcat, jpre, jcend, jcoff, jterm, jrun, jnil;      // device_tree_json's
 };
 
 }  // namespace
@@ -457,25 +721,17 @@ static void d2h_staged(ProtoState& P, uint8_t* buf, const uint8_t* d_src, uint64
     }
 }
 
-uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
-                           uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
-                           const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap, uint64_t* offsets) {
-    const DevView dv = device_view(S);
-    HIP_OK(hipSetDevice(dv.device));
-    std::lock_guard<std::mutex> lk(S.mu);
-    // KETO_PROTO_TRACE=1: phase times on stderr (tooling)
-    const bool trace = getenv("KETO_PROTO_TRACE") != nullptr;
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!trace) return;
-        (void)hipDeviceSynchronize();
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[proto] %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-        t_last = t;
-    };
-    ProtoState& P = proto_state(S, dv.device);
-    const hipStream_t st = 0;
-    // the arena's overlay rows and extra strings
+// the arena on the device for one encoder call: its overlay rows and extra strings next to the
+// snapshot's tables, its nodes and tree offsets
+namespace {
+struct Arena {
+    Tables T;
+    keto_tree_node* nodes;
+    uint64_t* toff;
+};
+Arena upload_arena(Snapshot& S, ProtoState& P, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
+                   uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
+                   const std::vector<std::string>& extra) {
     ProtoWork& W = P.work;
     DevStrs& ex = W.ex;
     ex.upload((uint32_t)extra.size(), [&](uint32_t i) { return std::string_view(extra[i]); });
@@ -500,12 +756,40 @@ uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_
         HIP_OK(hipMemcpy(d_oobj, oobj.data(), n_ov * 4, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(d_orel, orel.data(), n_ov * 4, hipMemcpyHostToDevice));
     }
-    Tables T{P.strs.view(), P.ns.view(), ex.view(), P.row_ns, P.row_obj, P.row_rel, P.n_rows, d_ons, d_oobj, d_orel,
-             ov_base, n_ov, extra_base};
-    keto_tree_node* d_nodes = W.nodes.get<keto_tree_node>(n_nodes);
-    uint64_t* d_toff = W.toff.get<uint64_t>(n_trees + 1ull);
-    HIP_OK(hipMemcpy(d_nodes, nodes, n_nodes * sizeof(keto_tree_node), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_toff, tree_off, (n_trees + 1ull) * 8, hipMemcpyHostToDevice));
+    Arena A;
+    A.T = Tables{P.strs.view(), P.ns.view(), ex.view(), P.row_ns, P.row_obj, P.row_rel, P.n_rows, d_ons, d_oobj, d_orel,
+                 ov_base, n_ov, extra_base};
+    A.nodes = W.nodes.get<keto_tree_node>(n_nodes);
+    A.toff = W.toff.get<uint64_t>(n_trees + 1ull);
+    HIP_OK(hipMemcpy(A.nodes, nodes, n_nodes * sizeof(keto_tree_node), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(A.toff, tree_off, (n_trees + 1ull) * 8, hipMemcpyHostToDevice));
+    return A;
+}
+}  // namespace
+
+uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
+                           uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
+                           const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap, uint64_t* offsets) {
+    const DevView dv = device_view(S);
+    HIP_OK(hipSetDevice(dv.device));
+    std::lock_guard<std::mutex> lk(S.mu);
+    // KETO_PROTO_TRACE=1: phase times on stderr (tooling)
+    const bool trace = getenv("KETO_PROTO_TRACE") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!trace) return;
+        (void)hipDeviceSynchronize();
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[proto] %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
+        t_last = t;
+    };
+    ProtoState& P = proto_state(S, dv.device);
+    const hipStream_t st = 0;
+    ProtoWork& W = P.work;
+    const Arena A = upload_arena(S, P, nodes, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra);
+    const Tables& T = A.T;
+    keto_tree_node* const d_nodes = A.nodes;
+    uint64_t* const d_toff = A.toff;
     lap("upload");
     uint64_t* d_slen = W.slen.get<uint64_t>(n_nodes);
     uint64_t* d_size = W.size.get<uint64_t>(n_nodes);
@@ -560,6 +844,93 @@ uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_
     uint8_t* d_out = W.out.get<uint8_t>(total);
     hipLaunchKernelGGL(proto_write, g(n_nodes), dim3(256), 0, st, d_nodes, n_nodes, T, d_slen, d_size, d_root, d_pos,
                        d_out);
+    HIP_OK(hipGetLastError());
+    lap("write");
+    d2h_staged(P, buf, d_out, total, st);
+    lap("d2h");
+    return total;
+}
+
+// Tree.MarshalJSON text of the same trees (the kernels above "json_"): nil[t] != 0 marks a nil tree
+// ("null"); a tree without nodes that is not nil (an error root) is empty.
+uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
+                          const uint8_t* nil, uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
+                          uint32_t extra_base, const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap,
+                          uint64_t* offsets) {
+    const DevView dv = device_view(S);
+    HIP_OK(hipSetDevice(dv.device));
+    std::lock_guard<std::mutex> lk(S.mu);
+    // KETO_JSON_TRACE=1: phase times on stderr (tooling)
+    const bool trace = getenv("KETO_JSON_TRACE") != nullptr;
+    auto t_last = std::chrono::steady_clock::now();
+    auto lap = [&](const char* what) {
+        if (!trace) return;
+        (void)hipDeviceSynchronize();
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[json] %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
+        t_last = t;
+    };
+    ProtoState& P = proto_state(S, dv.device);
+    const hipStream_t st = 0;
+    ProtoWork& W = P.work;
+    const Arena A = upload_arena(S, P, nodes, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra);
+    // run[t]: the "null" bytes of the node-less trees right before tree t, back to the last tree
+    // with nodes (several such trees in a row share one node index: they need a term per tree)
+    std::vector<uint64_t> run(n_trees + 1ull);
+    json_null_runs(tree_off, nil, n_trees, run.data());
+    uint64_t* d_run = W.jrun.get<uint64_t>(n_trees + 1ull);
+    uint8_t* d_nil = W.jnil.get<uint8_t>(n_trees);
+    HIP_OK(hipMemcpy(d_run, run.data(), (n_trees + 1ull) * 8, hipMemcpyHostToDevice));
+    if (n_trees) HIP_OK(hipMemcpy(d_nil, nil, n_trees, hipMemcpyHostToDevice));
+    lap("upload");
+    uint64_t* d_own = W.jown.get<uint64_t>(n_nodes);
+    uint64_t* d_clen = W.jclen.get<uint64_t>(n_nodes);
+    uint64_t* d_cat = W.jcat.get<uint64_t>(n_nodes + 1);
+    int64_t* d_pre = W.jpre.get<int64_t>(n_nodes + 1);
+    uint64_t* d_cend = W.jcend.get<uint64_t>(n_nodes);
+    uint64_t* d_coff = W.jcoff.get<uint64_t>(n_nodes);
+    uint64_t* d_term = W.jterm.get<uint64_t>(n_nodes + 2);
+    uint64_t* d_pos = W.pos.get<uint64_t>(n_nodes + 2);
+    uint64_t* d_st = W.st.get<uint64_t>(2 * n_nodes);
+    int64_t* d_uni = W.uni.get<int64_t>(n_nodes);
+    int64_t* d_lu = W.lu.get<int64_t>(n_nodes);
+    uint64_t* d_to = W.to.get<uint64_t>(n_trees + 1ull);
+    const auto g = [](uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, (n + 255) / 256)); };
+    size_t tb_max = 0, tb_sum = 0;
+    HIP_OK(hipcub::DeviceScan::InclusiveScan(nullptr, tb_max, d_uni, d_lu, hipcub::Max(), std::max<uint64_t>(1, n_nodes), st));
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_sum, d_term, d_pos, n_nodes + 2, st));
+    void* d_tmp = W.tmp.get<uint8_t>(std::max(tb_max, tb_sum));
+    HIP_OK(hipMemsetAsync(d_cat, 0, (n_nodes + 1) * 8, st));
+    HIP_OK(hipMemsetAsync(d_pre, 0xFF, (n_nodes + 1) * 8, st));          // -1: not a root
+    HIP_OK(hipMemsetAsync(d_term + n_nodes + 1, 0, 8, st));
+    hipLaunchKernelGGL(json_roots, g(n_trees + 1ull), dim3(256), 0, st, A.toff, n_trees, d_run, n_nodes, d_pre);
+    if (n_nodes) {
+        hipLaunchKernelGGL(json_own, g(n_nodes), dim3(256), 0, st, A.nodes, n_nodes, A.T, d_own, d_clen, d_uni);
+        HIP_OK(hipGetLastError());
+        lap("sizes");
+        HIP_OK(hipcub::DeviceScan::InclusiveScan(d_tmp, tb_max, d_uni, d_lu, hipcub::Max(), n_nodes, st));
+        hipLaunchKernelGGL(json_closes, g(n_trees), dim3(256), 0, st, A.nodes, A.toff, n_trees, d_lu, d_clen, d_cat, d_cend,
+                           d_coff, d_st);
+        HIP_OK(hipGetLastError());
+        lap("closes");
+    }
+    // exclusive scan over n_nodes + 2 entries (node n_nodes: what follows the last node; the last
+    // is 0): pos[n_nodes + 1] = total
+    hipLaunchKernelGGL(json_term, g(n_nodes + 1), dim3(256), 0, st, A.nodes, n_nodes, d_own, d_cat, d_pre, d_term);
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb_sum, d_term, d_pos, n_nodes + 2, st));
+    hipLaunchKernelGGL(json_trees, g(n_trees + 1ull), dim3(256), 0, st, A.toff, n_trees, d_run, d_nil, d_cat, d_pos,
+                       n_nodes, (uint8_t*)nullptr, d_to);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpy(offsets, d_to, (n_trees + 1ull) * 8, hipMemcpyDeviceToHost));
+    const uint64_t total = offsets[n_trees];
+    lap("scan");
+    if (!buf || cap < total || total == 0) return total;
+    uint8_t* d_out = W.out.get<uint8_t>(total);
+    if (n_nodes)
+        hipLaunchKernelGGL(json_write, g(n_nodes), dim3(256), 0, st, A.nodes, n_nodes, A.T, d_cat, d_pre, d_cend, d_coff,
+                           d_pos, d_out);
+    hipLaunchKernelGGL(json_trees, g(n_trees + 1ull), dim3(256), 0, st, A.toff, n_trees, d_run, d_nil, d_cat, d_pos,
+                       n_nodes, d_out, (uint64_t*)nullptr);
     HIP_OK(hipGetLastError());
     lap("write");
     d2h_staged(P, buf, d_out, total, st);

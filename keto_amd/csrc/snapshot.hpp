@@ -616,6 +616,12 @@ void mig_release(Snapshot& s);
 uint64_t device_tree_proto(Snapshot& s, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
                            uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
                            const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap, uint64_t* offsets);
+// Tree.MarshalJSON text of the same trees encoded on the device (proto.hip): nil[t] != 0 = a nil
+// tree ("null"); other trees without nodes are empty.  offsets and buf as device_tree_proto.
+uint64_t device_tree_json(Snapshot& s, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
+                          const uint8_t* nil, uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
+                          uint32_t extra_base, const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap,
+                          uint64_t* offsets);
 void device_copy(void* dst, const void* src, uint64_t bytes, void* stream);   // D2D, synchronous
 void device_memory(int device, uint64_t& free_bytes, uint64_t& total_bytes);
 // packed string requests resolved and checked on the device (resolve_dev.hip); the indexes of the

@@ -303,6 +303,29 @@ def config5(a, g=None):
             t = time.perf_counter() - t0
             assert got == json_bytes
             t_json = t if t_json is None else min(t_json, t)
+        # the same on the GPU (keto_tree_json_all_device), sizing + filling pair, best of 3: into fresh
+        # pageable numpy memory (the bounce chunks) and into a pinned keto_host_alloc buffer (one DMA);
+        # bytes and offsets compared with the host text
+        host_text = jbuf[:json_bytes].tobytes()
+        joffs_d = np.zeros(n + 1, dtype=np.uint64)
+        hb = HostBuffer(max(1, json_bytes), np.uint8)
+        t_jdev = {"pageable": None, "pinned": None}
+        jdev_equal = {"pageable": True, "pinned": True}
+        for kind in ("pageable", "pinned"):
+            for _ in range(3):
+                t0 = time.perf_counter()
+                total = lib.keto_tree_json_all_device(snap.h, arena, None, C.c_uint64(0),
+                                                      joffs_d.ctypes.data_as(C.c_void_p))
+                assert total == json_bytes, (total, lib.keto_last_error())
+                dst = np.empty(max(1, total), dtype=np.uint8) if kind == "pageable" else hb.array
+                got = lib.keto_tree_json_all_device(snap.h, arena, dst.ctypes.data_as(C.c_void_p), C.c_uint64(total),
+                                                    joffs_d.ctypes.data_as(C.c_void_p))
+                t = time.perf_counter() - t0
+                assert got == json_bytes
+                t_jdev[kind] = t if t_jdev[kind] is None else min(t_jdev[kind], t)
+                jdev_equal[kind] &= dst[:total].tobytes() == host_text and bool((joffs_d == joffs).all())
+        assert jdev_equal["pageable"] and jdev_equal["pinned"], jdev_equal
+        del hb
     finally:
         lib.keto_tree_arena_free(arena)
     # node-by-node comparison of a sample of trees with the oracle (pre-order, child order included)
@@ -364,6 +387,17 @@ def config5(a, g=None):
                      "MB_per_s": round(json_bytes / t_json / 1e6, 1),
                      "what": "keto_tree_json_all: every tree as Tree.MarshalJSON text, 16 host threads (sizing + "
                              "filling call)"},
+            "json_device": {"trees_per_s": round(n / t_jdev["pageable"], 1),
+                            "encode_ms": round(t_jdev["pageable"] * 1e3, 3),
+                            "MB_per_s": round(json_bytes / t_jdev["pageable"] / 1e6, 1),
+                            "pinned_encode_ms": round(t_jdev["pinned"] * 1e3, 3),
+                            "pinned_MB_per_s": round(json_bytes / t_jdev["pinned"] / 1e6, 1),
+                            "speedup_vs_host": round(t_json / t_jdev["pageable"], 2),
+                            "pinned_speedup_vs_host": round(t_json / t_jdev["pinned"], 2),
+                            "bytes_equal_host": jdev_equal["pageable"] and jdev_equal["pinned"],
+                            "what": "keto_tree_json_all_device: the same text encoded on the GPU (node upload, sizes, "
+                                    "closes, scan, write, D2H), sizing + filling call, into fresh pageable numpy memory "
+                                    "(pinned bounce chunks) and into a pinned caller buffer (keto_host_alloc)"},
             "parity": {"sample_trees": k, "sample_nodes": n_nodes, "mismatched_trees": bad}}
 
 
