@@ -19,14 +19,26 @@ _MEM_CLAUSE = ["-mllvm", "-amdgpu-sched-strategy=max-memory-clause"]
 SOURCE_FLAGS = {"engine.hip": _MEM_CLAUSE, "migrate.hip": _MEM_CLAUSE}
 
 
+def _csrc_includes(name, seen):
+    """`name` and the csrc headers it includes, transitively, each once, in include order."""
+    if name not in seen:
+        seen.append(name)
+        for line in open(os.path.join(CSRC, name), encoding="utf-8"):
+            inc = line.split('"')[1] if line.startswith('#include "') else ""
+            if inc and "/" not in inc and os.path.exists(os.path.join(CSRC, inc)):
+                _csrc_includes(inc, seen)
+    return seen
+
+
 def engine_build_id():
-    """sha256 of engine.hip and its compile flags: keys the committed PMC traffic profiles
-    (tools/traffic.py writes it, bench.py matches it)."""
+    """sha256 of what the tier-0 check kernel is compiled from: engine.hip, the csrc headers it
+    includes (hip_check.hpp, snapshot.hpp) and its compile flags.  Keys the committed PMC traffic
+    profiles (tools/traffic.py writes it, bench.py matches it)."""
     import hashlib
-    h = hashlib.sha256(open(os.path.join(CSRC, "engine.hip"), "rb").read())
-    flags = SOURCE_FLAGS.get("engine.hip", [])
-    if flags:
-        h.update(b"\0" + " ".join(flags).encode())
+    h = hashlib.sha256()
+    for name in _csrc_includes("engine.hip", []):
+        h.update(name.encode() + b"\0" + open(os.path.join(CSRC, name), "rb").read() + b"\0")
+    h.update(" ".join(SOURCE_FLAGS.get("engine.hip", [])).encode())
     return h.hexdigest()
 
 
@@ -37,25 +49,33 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _compile_cmd(src, obj, extra=()):
+    path = os.path.join(CSRC, src)
+    if src.endswith(".cpp"):
+        return [HIPCC, *CXXFLAGS, *HOST_HIP, *extra, "-x", "c++", "-c", path, "-o", obj]
+    return [HIPCC, f"--offload-arch={ARCH}", *CXXFLAGS, *SOURCE_FLAGS.get(src, []), *extra, "-c", path, "-o", obj]
+
+
+def _link_cmd(objs, out):
+    return [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out, *objs, "-L/opt/rocm/lib", "-lrccl"]
+
+
 def build(verbose=False, force=False):
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "parallel.hpp"), os.path.join(CSRC, "snapshot.hpp"), os.path.join(CSRC, "capi_internal.hpp"), os.path.join(CSRC, "json_runs.hpp"),
-                                                        os.path.join(HERE, "..", "include", "keto_mi355x.h"), os.path.abspath(__file__)]
-    if not force and not _stale(OUT, deps):
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
+    headers += [os.path.join(HERE, "..", "include", "keto_mi355x.h"), os.path.abspath(__file__)]
+    if not force and not _stale(OUT, [os.path.join(CSRC, s) for s in SOURCES] + headers):
         return OUT
     objs = []
     for src in SOURCES:
-        path = os.path.join(CSRC, src)
         obj = os.path.join(CSRC, src + ".o")
         objs.append(obj)
-        if not force and not _stale(obj, [path] + deps[len(SOURCES):]):
+        if not force and not _stale(obj, [os.path.join(CSRC, src)] + headers):
             continue
-        cmd = [HIPCC, f"--offload-arch={ARCH}", *CXXFLAGS, *SOURCE_FLAGS.get(src, []), "-c", path, "-o", obj]
-        if src.endswith(".cpp"):
-            cmd = [HIPCC, *CXXFLAGS, *HOST_HIP, "-x", "c++", "-c", path, "-o", obj]
+        cmd = _compile_cmd(src, obj)
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.check_call(cmd)
-    cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", OUT, *objs, "-L/opt/rocm/lib", "-lrccl"]
+    cmd = _link_cmd(objs, OUT)
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
@@ -72,15 +92,9 @@ def build_variant(name, defines):
     os.makedirs(vdir, exist_ok=True)
     objs = []
     for src in SOURCES:
-        path = os.path.join(CSRC, src)
         obj = os.path.join(vdir, f"{name}_{src}.o")
-        flags = [f"-D{d}" for d in defines]
-        if src.endswith(".cpp"):
-            cmd = [HIPCC, *CXXFLAGS, *HOST_HIP, *flags, "-x", "c++", "-c", path, "-o", obj]
-        else:
-            cmd = [HIPCC, f"--offload-arch={ARCH}", *CXXFLAGS, *SOURCE_FLAGS.get(src, []), *flags, "-c", path, "-o", obj]
-        subprocess.check_call(cmd)
+        subprocess.check_call(_compile_cmd(src, obj, [f"-D{d}" for d in defines]))
         objs.append(obj)
     out = os.path.join(vdir, f"lib_{name}.so")
-    subprocess.check_call([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", out, *objs, "-L/opt/rocm/lib", "-lrccl"])
+    subprocess.check_call(_link_cmd(objs, out))
     return out

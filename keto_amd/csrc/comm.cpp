@@ -47,17 +47,12 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "hip_check.hpp"
 
 using namespace keto;
 
 namespace {
 
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t err__ = (x);                                                                     \
-        if (err__ != hipSuccess)                                                                    \
-            throw Error{KETO_E_HIP, std::string(#x) + ": " + hipGetErrorString(err__)};             \
-    } while (0)
 #define NCCL_OK(x)                                                                                  \
     do {                                                                                            \
         ncclResult_t r__ = (x);                                                                     \

@@ -36,16 +36,10 @@
 #include <thread>
 #include <vector>
 
+#include "hip_check.hpp"
 #include "snapshot.hpp"
 
 namespace keto {
-
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t err__ = (x);                                                                     \
-        if (err__ != hipSuccess)                                                                    \
-            throw Error{KETO_E_HIP, std::string(#x) + ": " + hipGetErrorString(err__)};             \
-    } while (0)
 
 #ifndef KETO_CHECK_WAVES
 // check_kernel: 5 waves per SIMD (84 VGPRs).  At 7 (72 VGPRs) the kernel spilled 28-40 B per lane to
@@ -2732,6 +2726,31 @@ __global__ void __launch_bounds__(256) copy_big_runs(const CopyRun* __restrict__
 }
 
 // ------------------------------------------------------------------ host side
+// Tuning and test knobs are environment variables read on every call (tests set them per case);
+// clamping stays with the caller.
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+inline long long env_ll(const char* name, long long dflt) {
+    const char* e = getenv(name);
+    return e ? atoll(e) : dflt;
+}
+inline bool env_is(const char* name, int v) {   // set, and its integer value is v
+    const char* e = getenv(name);
+    return e && atoi(e) == v;
+}
+
+// The rows of the tier-0 kernel instance table (T0_TABLE): the eight KETO_T0 variants, the 8-frame
+// build, check_kernel and deep_wave_kernel for deep batches, the two streamed builds, the 8-wave
+// build for small batches, the three builds for wide arenas.
+enum T0Row {
+    T0_V0, T0_V1, T0_V2, T0_V3, T0_V4, T0_V5, T0_V6, T0_V7,
+    T0_F8, T0_CHECK, T0_DEEP_WAVE, T0_STREAM, T0_STREAM_V0, T0_W8, T0_WIDE4, T0_WIDE8, T0_WIDE_STREAM,
+    T0_ROWS
+};
+
 struct Tier {
     uint32_t n_slots = 0;
     uint32_t cap = 0;             // visited entries per slot (power of two)
@@ -2772,7 +2791,7 @@ struct DeviceState {
     WorkSet ws[2 + ASYNC_STREAMS];   // check workspaces (ws[1]: the second compute stream of the pipeline;
                                      // ws[2 + k]: packed batches checked without a host round trip, astream[k])
     WorkSet ews;                  // expand workspaces
-    uint32_t v1_lanes[16] = {};   // resident lanes of the tier-0 check kernel, per variant
+    uint32_t t0_lanes[T0_ROWS] = {};   // resident lanes of each tier-0 kernel instance (0 = not asked yet)
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;    // the pipeline's second compute stream (ws[1])
     hipStream_t astream[ASYNC_STREAMS] = {};   // device_check_rows_async: the checks, dealt in turn (ws[2 + k])
@@ -2921,8 +2940,7 @@ int hw_slots() {
     // persistent grid sized to residency: 256 CUs x 28 waves (7 per SIMD at the kernel's register
     // budget) x 64 lanes; every lane owns one visited table.  KETO_SLOTS overrides (tuning, tests;
     // read on every batch).
-    const char* e = getenv("KETO_SLOTS");
-    int s = e ? atoi(e) : 256 * 28 * 64;
+    int s = env_int("KETO_SLOTS", 256 * 28 * 64);
     s = (s + 255) / 256 * 256;
     return s < 256 ? 256 : s;
 }
@@ -3539,7 +3557,7 @@ bool apply_in_place(Snapshot& S) {
     std::lock_guard<std::mutex> lk(D.mu);
     lock_trace("apply: D.mu");
     HIP_OK(hipSetDevice(D.device));
-    const bool trace = getenv("KETO_APPLY_TRACE") != nullptr;          // tooling: phase times
+    const bool trace = env_set("KETO_APPLY_TRACE");          // tooling: phase times
     auto t_lap = std::chrono::steady_clock::now();
     std::string laps;
     auto lap = [&](const char* what) {
@@ -3942,8 +3960,8 @@ Plan make_plan(const DeviceState& D, uint32_t n, int frames_needed) {
     p.slots[0] = (uint32_t)std::min<uint64_t>((uint64_t)hw_slots(), ((uint64_t)n + 255) / 256 * 256);
     if (p.slots[0] == 0) p.slots[0] = 256;
     p.cap[0] = std::min<uint32_t>(256, full);
-    if (const char* e = getenv("KETO_TEST_T0_CAP"))      // test hook: push shallow requests up the tiers
-        p.cap[0] = std::min<uint32_t>(full, pow2_at_least((uint32_t)std::max(16, atoi(e))));
+    if (env_set("KETO_TEST_T0_CAP"))      // test hook: push shallow requests up the tiers
+        p.cap[0] = std::min<uint32_t>(full, pow2_at_least((uint32_t)std::max(16, env_int("KETO_TEST_T0_CAP", 16))));
     p.slots[1] = (uint32_t)std::min<uint64_t>(4096, ((uint64_t)n + 255) / 256 * 256);
     p.cap[1] = std::min<uint32_t>(1u << 15, full);
     // tier 2: tables that hold every visit id of the snapshot, as many lanes as 8 GiB allows (>= 1)
@@ -4302,9 +4320,61 @@ using CheckKernelFn = void (*)(DevSnap, DevOverlay, const keto_check_ids*, uint3
 // it runs 6 waves per SIMD against 8: its LDS columns hold 8 ids).  Variant 7 (12 + 8) ties.
 constexpr int T0_VARIANTS = 8;
 constexpr uint32_t KETO_HEAD_WORDS = 8 * 16 * 32;
+// The tier-0 kernel instances, one row each, in T0Row order (DeviceState::t0_lanes caches a row's
+// resident lanes under the same index).  check_core picks a row, asks t0_lanes() for its occupancy
+// and launches it; keto_check_kernel_name answers a row's name.
+struct T0Instance {
+    CheckKernelFn run;     // the build without work counters
+    CheckKernelFn count;   // the build with them; null = the instance has none
+    const char* name;
+};
+// <saved frames, save windows, LDS visit ids, register visit ids>
+#define KETO_T0_WAVE(F, WIN, LV, RV)                                                       \
+    {check_wave_kernel<F, WIN, LV, RV, false>, check_wave_kernel<F, WIN, LV, RV, true>,    \
+     "keto::check_wave_kernel<" #F ", " #WIN ", " #LV ", " #RV ", false, false>"}
+const T0Instance T0_TABLE[T0_ROWS] = {
+    KETO_T0_WAVE(4, false, 4, 16),    // T0_V0 .. T0_V7: the KETO_T0 variants
+    KETO_T0_WAVE(4, false, 4, 8),
+    KETO_T0_WAVE(4, false, 12, 4),
+    KETO_T0_WAVE(4, false, 8, 8),
+    KETO_T0_WAVE(4, false, 8, 6),
+    KETO_T0_WAVE(4, false, 12, 6),
+    KETO_T0_WAVE(4, false, 6, 8),
+    KETO_T0_WAVE(4, true, 8, 8),
+    KETO_T0_WAVE(8, false, 8, 8),     // T0_F8
+    {check_kernel<GlobalStack, false, 0>, check_kernel<GlobalStack, true, 0>, "keto::check_kernel<keto::GlobalStack, false, 0>"},
+    {deep_wave_kernel<8, 8, false>, deep_wave_kernel<8, 8, true>, "keto::deep_wave_kernel<8, 8, false>"},
+    // the streamed launch: the default variant's geometry (KETO_T0_STREAM=0: variant 0's)
+    {check_wave_kernel<4, false, 8, 8, false, true>, nullptr, "keto::check_wave_kernel<4, false, 8, 8, false, true>"},
+    {check_wave_kernel<4, false, 4, 16, false, true>, nullptr, "keto::check_wave_kernel<4, false, 4, 16, false, true>"},
+    {check_wave_kernel_w8<4, 4, 16>, nullptr, "keto::check_wave_kernel_w8<4, 4, 16>"},
+    {check_wave_kernel_wide<4, false>, nullptr, "keto::check_wave_kernel_wide<4, false>"},
+    {check_wave_kernel_wide<8, false>, nullptr, "keto::check_wave_kernel_wide<8, false>"},
+    {check_wave_kernel_wide<4, true>, nullptr, "keto::check_wave_kernel_wide<4, true>"},
+};
+#undef KETO_T0_WAVE
+// a row's resident lanes: the persistent grid is what is resident at the kernel's register / LDS
+// budget (KETO_SLOTS overrides)
+uint32_t t0_lanes(DeviceState& D, T0Row row) {
+    if (!D.t0_lanes[row]) {
+        int per_cu = 0, cus = 0;
+        HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, T0_TABLE[row].run, 256, 0));
+        HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, D.device));
+        D.t0_lanes[row] = (uint32_t)std::max(1, per_cu) * (uint32_t)std::max(1, cus) * 256u;
+    }
+    return D.t0_lanes[row];
+}
+// the workset's run heads with their first `words` words cleared on `st`
+uint32_t* cleared_heads(WorkSet& W, uint32_t words, hipStream_t st) {
+    if (!W.heads) {
+        uint64_t acc = 0;
+        W.heads = dmalloc<uint32_t>(KETO_HEAD_WORDS, acc);
+    }
+    HIP_OK(hipMemsetAsync(W.heads, 0, words * sizeof(uint32_t), st));
+    return W.heads;
+}
 int t0_variant() {
-    const char* e = getenv("KETO_T0");
-    const int v = e ? atoi(e) : 3;
+    const int v = env_int("KETO_T0", 3);
     return v >= 0 && v < T0_VARIANTS ? v : 3;
 }
 // request runs handed out per grab by the tier-0 wave kernel (TierArgs::dyn) for a batch of n
@@ -4317,14 +4387,10 @@ int t0_variant() {
 // the static eighths, KETO_T0_HEADS the heads per XCD, KETO_T0_DYN_FORCE=1 drops the batch-size
 // condition (tests).
 uint32_t t0_dyn(uint64_t n, uint64_t lanes) {
-    const char* e = getenv("KETO_T0_DYN");
-    const char* f = getenv("KETO_T0_DYN_STATIC");       // eighths of a range handed out statically
-    const char* force = getenv("KETO_T0_DYN_FORCE");
-    if (!(force && atoi(force) == 1) && n < 16 * lanes) return 0u;
-    const char* hs = getenv("KETO_T0_HEADS");          // heads per XCD (a power of two, <= 16)
-    const int v = e ? atoi(e) : 4;
-    const int st = f ? std::min(7, std::max(0, atoi(f))) : 2;
-    const int heads = hs ? std::min(16, atoi(hs)) : 4;
+    if (!env_is("KETO_T0_DYN_FORCE", 1) && n < 16 * lanes) return 0u;
+    const int v = env_int("KETO_T0_DYN", 4);
+    const int st = std::min(7, std::max(0, env_int("KETO_T0_DYN_STATIC", 2)));   // eighths of a range handed out statically
+    const int heads = std::min(16, env_int("KETO_T0_HEADS", 4));                 // heads per XCD (a power of two, <= 16)
     uint32_t hl2 = 0;
     while ((1 << (hl2 + 1)) <= heads) ++hl2;
     return v > 0 ? (std::min<uint32_t>((uint32_t)v + 3u, 0xFFFCu) & ~3u) | ((uint32_t)st << 16) | (hl2 << 20) : 0u;
@@ -4332,46 +4398,16 @@ uint32_t t0_dyn(uint64_t n, uint64_t lanes) {
 // streamed batches: runs of 4 (a power of two, so no run straddles a chunk), all of them dealt by
 // the heads (no static part: a lane's static run could lie in the last chunk)
 uint32_t t0_stream_dyn() {
-    const char* hs = getenv("KETO_T0_HEADS");
-    const int heads = hs ? std::min(16, atoi(hs)) : 4;
+    const int heads = std::min(16, env_int("KETO_T0_HEADS", 4));
     uint32_t hl2 = 0;
     while ((1 << (hl2 + 1)) <= heads) ++hl2;
     return 4u | (hl2 << 20);
 }
-const char* t0_kernel_name(int var) {
-    switch (var) {
-        case 0: return "keto::check_wave_kernel<4, false, 4, 16, false, false>";
-        case 1: return "keto::check_wave_kernel<4, false, 4, 8, false, false>";
-        case 2: return "keto::check_wave_kernel<4, false, 12, 4, false, false>";
-        case 3: return "keto::check_wave_kernel<4, false, 8, 8, false, false>";
-        case 4: return "keto::check_wave_kernel<4, false, 8, 6, false, false>";
-        case 5: return "keto::check_wave_kernel<4, false, 12, 6, false, false>";
-        case 6: return "keto::check_wave_kernel<4, false, 6, 8, false, false>";
-        case 7: return "keto::check_wave_kernel<4, true, 8, 8, false, false>";
-        default: return "keto::check_wave_kernel<8, false, 8, 8, false, false>";
-    }
-}
-CheckKernelFn t0_kernel(int var, bool count) {
-    // <saved frames, save windows, LDS visit ids, register visit ids>
-    switch (var) {
-        case 0: return count ? check_wave_kernel<4, false, 4, 16, true> : check_wave_kernel<4, false, 4, 16, false>;
-        case 1: return count ? check_wave_kernel<4, false, 4, 8, true> : check_wave_kernel<4, false, 4, 8, false>;
-        case 2: return count ? check_wave_kernel<4, false, 12, 4, true> : check_wave_kernel<4, false, 12, 4, false>;
-        case 3: return count ? check_wave_kernel<4, false, 8, 8, true> : check_wave_kernel<4, false, 8, 8, false>;
-        case 4: return count ? check_wave_kernel<4, false, 8, 6, true> : check_wave_kernel<4, false, 8, 6, false>;
-        case 5: return count ? check_wave_kernel<4, false, 12, 6, true> : check_wave_kernel<4, false, 12, 6, false>;
-        case 6: return count ? check_wave_kernel<4, false, 6, 8, true> : check_wave_kernel<4, false, 6, 8, false>;
-        case 7: return count ? check_wave_kernel<4, true, 8, 8, true> : check_wave_kernel<4, true, 8, 8, false>;
-        default: return count ? check_wave_kernel<8, false, 8, 8, true> : check_wave_kernel<8, false, 8, 8, false>;
-    }
-}
-// the streamed launch: the default variant's geometry (KETO_T0_STREAM=0: variant 0's)
-bool t0_stream_v0() {
-    const char* e = getenv("KETO_T0_STREAM");
-    return e && atoi(e) == 0;
-}
-CheckKernelFn t0_stream_kernel() {
-    return t0_stream_v0() ? check_wave_kernel<4, false, 4, 16, false, true> : check_wave_kernel<4, false, 8, 8, false, true>;
+bool t0_stream_v0() { return env_is("KETO_T0_STREAM", 0); }
+// the row a batch of `fr` frames takes by its depth and the environment alone (`dw`: deep_wave_kernel
+// for a deep batch); check_core then looks at the batch itself
+T0Row t0_row_by_depth(int fr, bool dw) {
+    return fr <= 4 ? (T0Row)t0_variant() : fr <= 8 ? T0_F8 : dw ? T0_DEEP_WAVE : T0_CHECK;
 }
 }  // namespace
 
@@ -4380,15 +4416,12 @@ CheckKernelFn t0_stream_kernel() {
 // dependent accesses per DFS step either way, and its 16K-entry maps overflow to tier 1 where the
 // inline kernel borrows in place; profiles/r02j_deep_sweep.log)
 bool deep_wave(int32_t gmd) {
-    const char* e = getenv("KETO_DEEP_WAVE");
-    return gmd - 1 <= DF && e && atoi(e) == 1;
+    return gmd - 1 <= DF && env_is("KETO_DEEP_WAVE", 1);
 }
 
 const char* device_check_kernel_name(int32_t gmd) {
     const int fr = std::max(1, std::min<int32_t>(gmd, 65535) - 1);
-    if (fr > 8 && deep_wave(gmd)) return "keto::deep_wave_kernel<8, 8, false>";
-    if (fr > 8) return "keto::check_kernel<keto::GlobalStack, false, 0>";
-    return t0_kernel_name(fr <= 4 ? t0_variant() : T0_VARIANTS);
+    return T0_TABLE[t0_row_by_depth(fr, deep_wave(gmd))].name;
 }
 
 namespace {
@@ -4468,8 +4501,7 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
         if ((ids + 3) / 4 > 0xFFFFFFFFull) throw Error{KETO_E_RANGE, "tier-2 visited table exceeds 2^32 words"};
         p.cap[2] = (uint32_t)((ids + 3) / 4);
         const uint64_t per = (uint64_t)p.cap[2] * sizeof(uint64_t);
-        const char* es = getenv("KETO_T2_SLOTS");
-        const uint64_t want = std::min<uint64_t>(es ? (uint64_t)atoi(es) : 256u, std::max<uint64_t>(1, (16ull << 30) / per));
+        const uint64_t want = std::min<uint64_t>((uint64_t)env_int("KETO_T2_SLOTS", 256), std::max<uint64_t>(1, (16ull << 30) / per));
         uint32_t s2 = 1;
         while (s2 * 2 <= want) s2 *= 2;
         p.slots[2] = s2;
@@ -4477,50 +4509,25 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
     // (deep_wave_kernel keeps one segment bit: arenas of up to 2 segments)
     const bool dw = kind == 2 && deep_wave(gmd) && (uint64_t)D.n_units <= (1ull << 31) && D.root_g == 0;
     if (ss && kind != 0) throw Error{KETO_E_INVALID, "streamed batches need max-depth <= 5"};
-    int var = ss ? T0_VARIANTS + 3 + (t0_stream_v0() ? 1 : 0)
-                 : kind == 0 ? t0_variant() : kind == 1 ? T0_VARIANTS : dw ? T0_VARIANTS + 2 : T0_VARIANTS + 1;
-    // batches of fewer than 16 requests per lane of the 8-wave build take check_wave_kernel_w8
-    // (variant 0's geometry at 8 waves per SIMD); KETO_T0 (tuning) or KETO_T0_W8=0 keep the variant
-    constexpr int VAR_W8 = T0_VARIANTS + 5;
     // a wide arena (past 64 GiB) takes check_wave_kernel_wide as tier 0, whatever the variant
     const bool wide = D.root_g != 0;
-    if (kind == 0 && !ss && !work_out && !wide && !getenv("KETO_T0") && !(getenv("KETO_T0_W8") && atoi(getenv("KETO_T0_W8")) == 0)) {
-        if (!D.v1_lanes[VAR_W8]) {
-            int per_cu = 0, cus = 0;
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, check_wave_kernel_w8<4, 4, 16>, 256, 0));
-            HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, D.device));
-            D.v1_lanes[VAR_W8] = (uint32_t)std::max(1, per_cu) * (uint32_t)std::max(1, cus) * 256u;
-        }
-        if ((uint64_t)n < 16ull * D.v1_lanes[VAR_W8]) var = VAR_W8;
-    }
-    if (!D.v1_lanes[var]) {
-        // persistent grid = what is resident at the kernel's register / LDS budget (KETO_SLOTS overrides)
-        int per_cu = 0, cus = 0;
-        if (ss && wide)
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, check_wave_kernel_wide<4, true>, 256, 0));
-        else if (ss)
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, t0_stream_kernel(), 256, 0));
-        else if (wide && kind < 2)
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &per_cu, kind == 0 ? check_wave_kernel_wide<4, false> : check_wave_kernel_wide<8, false>, 256, 0));
-        else if (dw)
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, deep_wave_kernel<8, 8, false>, 256, 0));
-        else if (kind == 2)
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, check_kernel<GlobalStack, false, 0>, 256, 0));
-        else
-            HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, t0_kernel(var, false), 256, 0));
-        HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, D.device));
-        D.v1_lanes[var] = (uint32_t)std::max(1, per_cu) * (uint32_t)std::max(1, cus) * 256u;
-    }
-    uint32_t lanes = getenv("KETO_SLOTS") ? (uint32_t)hw_slots() : D.v1_lanes[var];
+    T0Row row = t0_row_by_depth(fr, dw);
+    if (ss) row = wide ? T0_WIDE_STREAM : t0_stream_v0() ? T0_STREAM_V0 : T0_STREAM;
+    else if (wide && kind < 2) row = kind == 0 ? T0_WIDE4 : T0_WIDE8;
+    // batches of fewer than 16 requests per lane of the 8-wave build take check_wave_kernel_w8
+    // (variant 0's geometry at 8 waves per SIMD); KETO_T0 (tuning) or KETO_T0_W8=0 keep the variant
+    else if (kind == 0 && !work_out && !env_set("KETO_T0") && !env_is("KETO_T0_W8", 0) &&
+             (uint64_t)n < 16ull * t0_lanes(D, T0_W8))
+        row = T0_W8;
+    const T0Instance& inst = T0_TABLE[row];
+    uint32_t lanes = env_set("KETO_SLOTS") ? (uint32_t)hw_slots() : t0_lanes(D, row);
     // a batch of at most ~2 requests per resident lane (config #2: 1M requests) takes one lane per
     // request: the grid is then more than the chip holds at once, and a wave that finishes makes room
     // for the next instead of a lane walking its second request behind its first (0.158 -> 0.144
     // ms, profiles/r05aa_config2_grid.log).  KETO_T0_ONE_PER_LANE = the requests-per-lane bound
     // (default 2; 0 = off); tier-0 tables: 2 KB per lane
-    if (var == VAR_W8 && !getenv("KETO_SLOTS")) {
-        const char* e1 = getenv("KETO_T0_ONE_PER_LANE");
-        const uint64_t k = e1 ? (uint64_t)std::max(0, atoi(e1)) : 2u;
+    if (row == T0_W8 && !env_set("KETO_SLOTS")) {
+        const uint64_t k = (uint64_t)std::max(0, env_int("KETO_T0_ONE_PER_LANE", 2));
         if ((uint64_t)n <= k * lanes) lanes = (uint32_t)(((uint64_t)n + 255) / 256 * 256);
     }
     p.slots[0] = (uint32_t)std::min<uint64_t>(lanes, ((uint64_t)n + 255) / 256 * 256);
@@ -4529,15 +4536,14 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
         // kernels, which a launch holding every slot starves until its lanes give up waiting
         // (tools/dev/stream_probe.hip: 8/8 of the slots never saw a chunk land, 7/8 did).
         // KETO_STREAM_EIGHTHS overrides the share (default 7)
-        const char* e8 = getenv("KETO_STREAM_EIGHTHS");
-        const uint32_t eighths = (uint32_t)std::min(8, std::max(1, e8 ? atoi(e8) : 7));
+        const uint32_t eighths = (uint32_t)std::min(8, std::max(1, env_int("KETO_STREAM_EIGHTHS", 7)));
         p.slots[0] = std::max<uint32_t>(256, p.slots[0] / 8 * eighths / 256 * 256);
     }
     if (stash && kind < 2) {
         // KETO_CHUNK_LANES (tuning): a pipeline chunk's tier 0 on at most that many lanes, so that the
         // chunks of two compute streams (KETO_PIPE_STREAMS=2) can run side by side
-        if (const char* e = getenv("KETO_CHUNK_LANES"))
-            p.slots[0] = std::max<uint32_t>(256, std::min<uint32_t>(p.slots[0], (uint32_t)atoi(e) / 256 * 256));
+        if (env_set("KETO_CHUNK_LANES"))
+            p.slots[0] = std::max<uint32_t>(256, std::min<uint32_t>(p.slots[0], (uint32_t)env_int("KETO_CHUNK_LANES", 0) / 256 * 256));
     }
     if (kind == 2) {
         // deep requests (nested groups) visit thousands of sets.  Tier 0 gets tables of 64K entries
@@ -4552,8 +4558,8 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
         uint64_t held = 0;
         for (int l = 0; l < 2; ++l) held += (uint64_t)W.tiers[l].n_slots * W.tiers[l].cap * sizeof(uint64_t);
         uint64_t budget = std::min<uint64_t>(total_b / 2, (free_b + held) * 6 / 10);
-        if (const char* eb = getenv("KETO_DEEP_BUDGET_GB"))
-            budget = std::min<uint64_t>((uint64_t)atoi(eb) << 30, (free_b + held) * 3 / 4);
+        if (env_set("KETO_DEEP_BUDGET_GB"))
+            budget = std::min<uint64_t>((uint64_t)env_int("KETO_DEEP_BUDGET_GB", 0) << 30, (free_b + held) * 3 / 4);
         const uint64_t b0 = budget / 4 * 3, b1 = budget - b0;
         const uint32_t full = pow2_at_least(2ull * D.vid_bound + 2);
         auto fit = [&](uint32_t slots, uint32_t lo, uint32_t hi, uint64_t b) {
@@ -4561,20 +4567,17 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
             while (c < hi && (uint64_t)slots * (2ull * c) * sizeof(uint64_t) <= b) c *= 2;
             return std::min(c, full);
         };
-        const char* e0 = getenv("KETO_T0_CAP");
-        const char* e1 = getenv("KETO_T1_SLOTS");
-        const char* e2 = getenv("KETO_T1_CAP");
-        const uint32_t want0 = std::min(full, pow2_at_least(e0 ? (uint32_t)std::max(256, atoi(e0)) : 65536u));
-        if (!getenv("KETO_SLOTS")) {
+        const uint32_t want0 = std::min(full, pow2_at_least((uint32_t)std::max(256, env_int("KETO_T0_CAP", 65536))));
+        if (!env_set("KETO_SLOTS")) {
             const uint64_t fit_lanes = std::max<uint64_t>(256, b0 / ((uint64_t)want0 * sizeof(uint64_t)) / 256 * 256);
             p.slots[0] = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(lanes, fit_lanes), ((uint64_t)n + 255) / 256 * 256);
         }
         p.cap[0] = fit(p.slots[0], 256, want0, b0);
-        p.slots[1] = (uint32_t)std::min<uint64_t>(e1 ? (uint32_t)atoi(e1) : 16384u, ((uint64_t)n + 255) / 256 * 256);
-        p.cap[1] = std::max(p.cap[0], fit(p.slots[1], 1024, e2 ? (uint32_t)atoi(e2) : 131072u, b1));
-        p.pool = getenv("KETO_NO_POOL") == nullptr;
+        p.slots[1] = (uint32_t)std::min<uint64_t>((uint32_t)env_int("KETO_T1_SLOTS", 16384), ((uint64_t)n + 255) / 256 * 256);
+        p.cap[1] = std::max(p.cap[0], fit(p.slots[1], 1024, (uint32_t)env_int("KETO_T1_CAP", 131072), b1));
+        p.pool = !env_set("KETO_NO_POOL");
     }
-    if (const char* e = getenv("KETO_TEST_T2_FRAMES")) p.frames[2] = 2 * std::max(1, atoi(e));   // test hook
+    if (env_set("KETO_TEST_T2_FRAMES")) p.frames[2] = 2 * std::max(1, env_int("KETO_TEST_T2_FRAMES", 1));   // test hook
     DevSnap sv = D.view();
     unsigned long long* dwork = nullptr;
     if (work_out) {
@@ -4594,17 +4597,9 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
                       a.item_owner = items->owner;
                       a.item_acc = items->acc;
                   }
-                  if (level == 0 && kind == 2 && !dw) {
+                  if (level == 0 && row == T0_CHECK) {
                       // deep tier 0: one request per grab after each lane's first (KETO_T0_NEXT=0: runs)
-                      const char* en = getenv("KETO_T0_NEXT");
-                      if (!(en && atoi(en) == 0)) {
-                          if (!W.heads) {
-                              uint64_t acc = 0;
-                              W.heads = dmalloc<uint32_t>(KETO_HEAD_WORDS, acc);
-                          }
-                          HIP_OK(hipMemsetAsync(W.heads, 0, sizeof(uint32_t), st));
-                          a.next = W.heads;
-                      }
+                      if (!env_is("KETO_T0_NEXT", 0)) a.next = cleared_heads(W, 1, st);
                   }
                   if (level < 2 && p.pool) {
                       const Tier& tn = W.tiers[level + 1];
@@ -4639,30 +4634,12 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
                       a.stalled = ss->stalled;
                       a.wait_ticks = ss->wait_ticks;
                       a.dyn = t0_stream_dyn();
-                      if (!W.heads) {
-                          uint64_t acc = 0;
-                          W.heads = dmalloc<uint32_t>(KETO_HEAD_WORDS, acc);
-                      }
-                      HIP_OK(hipMemsetAsync(W.heads, 0, KETO_HEAD_WORDS * sizeof(uint32_t), st));
-                      a.heads = W.heads;
-                      if (wide) go(check_wave_kernel_wide<4, true>);
-                      else go(t0_stream_kernel());
+                      a.heads = cleared_heads(W, KETO_HEAD_WORDS, st);
                   }
                   else if (level == 0 && kind < 2) {
                       a.dyn = t0_dyn(n, slots);
-                      if (const char* wc = getenv("KETO_T0_WALK"))
-                          if (atoi(wc) > 0) a.walk_cap = (uint32_t)atoi(wc);
-                      if (a.dyn) {
-                          if (!W.heads) {
-                              uint64_t acc = 0;
-                              W.heads = dmalloc<uint32_t>(KETO_HEAD_WORDS, acc);
-                          }
-                          HIP_OK(hipMemsetAsync(W.heads, 0, KETO_HEAD_WORDS * sizeof(uint32_t), st));
-                          a.heads = W.heads;
-                      }
-                      if (var == VAR_W8) go(check_wave_kernel_w8<4, 4, 16>);
-                      else if (wide) kind == 0 ? go(check_wave_kernel_wide<4, false>) : go(check_wave_kernel_wide<8, false>);
-                      else go(t0_kernel(var, dwork != nullptr));
+                      if (const int wc = env_int("KETO_T0_WALK", 0); wc > 0) a.walk_cap = (uint32_t)wc;
+                      if (a.dyn) a.heads = cleared_heads(W, KETO_HEAD_WORDS, st);
                   }
                   else if (level == 0 && dw) {
                       // frames: the tier's GlobalStack area as [frame][lane] 8-B words (DF per lane)
@@ -4671,19 +4648,11 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
                           throw Error{KETO_E_RANGE, "deep frame area too small"};
                       // items (one long search can take 30K+ iterations): every work request dealt one at a
                       // time by the XCD heads, so no lane holds two long searches back to back
-                      a.dyn = items ? 1u : getenv("KETO_T0_DYN_FORCE") ? t0_dyn(n, slots) : 0u;
-                      if (a.dyn) {
-                          if (!W.heads) {
-                              uint64_t acc = 0;
-                              W.heads = dmalloc<uint32_t>(KETO_HEAD_WORDS, acc);
-                          }
-                          HIP_OK(hipMemsetAsync(W.heads, 0, KETO_HEAD_WORDS * sizeof(uint32_t), st));
-                          a.heads = W.heads;
-                      }
-                      dwork ? go(deep_wave_kernel<8, 8, true>) : go(deep_wave_kernel<8, 8, false>);
+                      a.dyn = items ? 1u : env_set("KETO_T0_DYN_FORCE") ? t0_dyn(n, slots) : 0u;
+                      if (a.dyn) a.heads = cleared_heads(W, KETO_HEAD_WORDS, st);
                   }
-                  else if (level == 0)
-                      dwork ? go(check_kernel<GlobalStack, true, 0>) : go(check_kernel<GlobalStack, false, 0>);
+                  if (level == 0)
+                      go(dwork && inst.count ? inst.count : inst.run);
                   else if (level == 2)         // direct-indexed visited tables (DirectVisited)
                       dwork ? go(check_kernel<GlobalStack, true, 2>) : go(check_kernel<GlobalStack, false, 2>);
                   else if (local)
@@ -4698,7 +4667,7 @@ void check_core(Snapshot& S, DeviceState& D, const keto_check_ids* dq, uint32_t 
         HIP_OK(hipMemcpyAsync(h, dwork, sizeof(h), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
         for (int i = 0; i < KETO_WORK_SLOTS; ++i) work_out[i] = h[i];
-        if (getenv("KETO_SIMT_PROF"))       // tier-0 SIMT profile (tooling): wave / lane counts
+        if (env_set("KETO_SIMT_PROF"))       // tier-0 SIMT profile (tooling): wave / lane counts
             fprintf(stderr, "simt: iter %llu/%llu work %llu/%llu walk %llu/%llu enter %llu/%llu\n", h[16], h[17],
                     h[18], h[19], h[20], h[21], h[22], h[23]);
     }
@@ -4813,24 +4782,9 @@ __global__ void __launch_bounds__(256) pairs_to_handles(const keto_check_pair* _
                                                         uint32_t n_rows, uint32_t* misrouted) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const keto_check_pair p = in[i];
-    keto_check_ids q{KETO_NO_ROW, KETO_NO_TARGET, 0u, depth};
-    if (p.row != KETO_NO_ROW) {
-        const uint32_t h = p.row < n_rows ? table[p.row] : NO_UNIT;
-        if (h == NO_UNIT) atomicAdd(misrouted, 1u);
-        q.row = h == NO_UNIT ? KETO_NO_ROW : h;
-    }
-    if (p.subject != KETO_NO_TARGET) {
-        if (p.subject & EDGE_SET) {
-            const uint32_t r = p.subject & EDGE_VAL;
-            const uint32_t h = r < n_rows ? table[r] : NO_UNIT;
-            q.target = h == NO_UNIT ? KETO_NO_TARGET : h;
-            q.flags = 1u;
-        } else {
-            q.target = p.subject;
-        }
-    }
-    out[i] = q;
+    bool mis;
+    out[i] = pair_to_ids(in[i], depth, table, n_rows, mis);
+    if (mis) atomicAdd(misrouted, 1u);
 }
 
 void translate_pairs_locked(Snapshot& S, DeviceState& D, const keto_check_pair* d_reqs, keto_check_ids* d_out, uint32_t n,
@@ -4853,14 +4807,12 @@ bool host_pinned(const void* p) {
 }
 
 uint64_t chunk_requests() {
-    const char* e = getenv("KETO_CHUNK");               // tuning / tests
-    const long long v = e ? atoll(e) : (4ll << 20);
+    const long long v = env_ll("KETO_CHUNK", 4ll << 20);               // tuning / tests
     return (uint64_t)std::max<long long>(256, v);
 }
 // the first chunk of a host batch: shorter, so the check starts after a shorter copy
 uint64_t first_chunk_requests(uint64_t C) {
-    const char* e = getenv("KETO_CHUNK_FIRST");         // tuning / tests
-    const long long v = e ? atoll(e) : (long long)C;
+    const long long v = env_ll("KETO_CHUNK_FIRST", (long long)C);         // tuning / tests
     return (uint64_t)std::min<long long>((long long)C, std::max<long long>(256, v));
 }
 
@@ -4883,10 +4835,8 @@ namespace {
 // Streamed host batches: FORM_PAIRS from pinned memory, no overlay, max-depth <= 5, at least
 // KETO_STREAM_MIN requests (default 1M); KETO_STREAM=0 turns it off
 bool stream_ok(const Snapshot& S, uint32_t n, int32_t gmd, const Overlay* ovh) {
-    const char* e = getenv("KETO_STREAM");
-    if (e && atoi(e) == 0) return false;
-    const char* m = getenv("KETO_STREAM_MIN");
-    const uint64_t lo = m ? strtoull(m, nullptr, 10) : (1ull << 20);
+    if (env_is("KETO_STREAM", 0)) return false;
+    const uint64_t lo = (uint64_t)env_ll("KETO_STREAM_MIN", 1ll << 20);
     return n >= std::max<uint64_t>(lo, 1) && !(ovh && !ovh->empty()) && std::max(1, std::min(gmd, 65535) - 1) <= 4 &&
            S.part_mode != PART_MIGRATE;
 }
@@ -4901,8 +4851,7 @@ bool stream_ok(const Snapshot& S, uint32_t n, int32_t gmd, const Overlay* ovh) {
 bool check_streamed(Snapshot& S, DeviceState& D, const keto_check_pair* reqs, uint32_t n, int32_t gmd, uint8_t* allowed,
                     int32_t depth) {
     uint64_t acc = 0;
-    const char* ec = getenv("KETO_STREAM_CHUNK_LOG2");
-    const uint32_t cl = (uint32_t)std::min(26, std::max(16, ec ? atoi(ec) : 20));
+    const uint32_t cl = (uint32_t)std::min(26, std::max(16, env_int("KETO_STREAM_CHUNK_LOG2", 20)));
     const uint64_t chunks = ((uint64_t)n + (1ull << cl) - 1) >> cl;
     if (D.st_cap < n) {
         for (void* p : {(void*)D.st_pairs, (void*)D.st_dec, (void*)D.st_x, (void*)D.st_ready})
@@ -4926,20 +4875,19 @@ bool check_streamed(Snapshot& S, DeviceState& D, const keto_check_pair* reqs, ui
     HIP_OK(hipMemsetAsync(D.st_ready, 0, chunks * sizeof(uint32_t), D.stream));
     HIP_OK(hipEventRecord(D.pev[6], D.stream));
     HIP_OK(hipStreamWaitEvent(D.copy_in, D.pev[6], 0));
-    const bool drop = getenv("KETO_STREAM_TEST_DROP") != nullptr;           // test hook: the last chunk is never marked
+    const bool drop = env_set("KETO_STREAM_TEST_DROP");           // test hook: the last chunk is never marked
     for (uint64_t c = 0; c < chunks; ++c) {
         const uint64_t lo = c << cl, len = std::min<uint64_t>(n, lo + (1ull << cl)) - lo;
         HIP_OK(hipMemcpyAsync(D.st_pairs + lo, reqs + lo, len * sizeof(keto_check_pair), hipMemcpyHostToDevice, D.copy_in));
         if (!(drop && c + 1 == chunks)) HIP_OK(hipStreamWriteValue32(D.copy_in, D.st_ready + c, 1u, 0));
     }
-    const char* ew = getenv("KETO_STREAM_WAIT_MS");
     StreamSrc ss;
     ss.pairs = D.st_pairs;
     ss.ready = D.st_ready;
     ss.chunk_log2 = cl;
     ss.depth = depth;
     ss.stalled = W.counters + 5;
-    ss.wait_ticks = (uint64_t)std::max(1, ew ? atoi(ew) : 1000) * 100000ull;   // wall clock: 100 MHz
+    ss.wait_ticks = (uint64_t)std::max(1, env_int("KETO_STREAM_WAIT_MS", 1000)) * 100000ull;   // wall clock: 100 MHz
     ss.xlate = D.st_x;
     check_core(S, D, nullptr, n, gmd, D.st_dec, D.stream, DevOverlay{nullptr, 0xFFFFFFFFu}, nullptr, false, nullptr,
                nullptr, 0, nullptr, &ss);
@@ -5053,8 +5001,7 @@ void device_check_host(Snapshot& S, const void* reqs_v, uint32_t n, int32_t gmd,
     // (ws[0], ws[1]), so that a chunk's check could start while the previous one drains its tail.
     // Measured no faster (4.64-4.77 vs 4.59 ms per 16.7M batch, profiles/r02aq_pipe_streams.log):
     // one stream stays the default
-    const char* eps = getenv("KETO_PIPE_STREAMS");
-    const bool two = eps && atoi(eps) == 2;
+    const bool two = env_is("KETO_PIPE_STREAMS", 2);
     if (two && !D.stream2) HIP_OK(hipStreamCreateWithFlags(&D.stream2, hipStreamNonBlocking));
     hipEvent_t setup_done = D.pev[6];
     HIP_OK(hipEventRecord(setup_done, D.stream));
@@ -5427,7 +5374,7 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     if (gmd > 65535) gmd = 65535;
     hipStream_t st = D.stream;
     // KETO_EXPAND_TRACE=1: phase times on stderr (tooling)
-    const bool trace = getenv("KETO_EXPAND_TRACE") != nullptr;
+    const bool trace = env_set("KETO_EXPAND_TRACE");
     auto t_last = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!trace) return;
@@ -5467,25 +5414,22 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     // did not fit (or that a later tier decided, counting only) are filled by a second pass over just
     // them.  KETO_EXPAND_STAGE=0: count pass + fill pass over every root (the two-pass form); =N > 1:
     // N nodes of staging per lane.
-    const char* se = getenv("KETO_EXPAND_STAGE");
-    const bool staged = !se || atoi(se) != 0;
+    const int se = env_int("KETO_EXPAND_STAGE", 1);
+    const bool staged = se != 0;
     uint64_t stage_cap = 0, ovf_chunk = 0, ovf_cap = 0, ovf_base = 0;
     if (staged) {
         // staging nodes: KETO_EXPAND_STAGE_MB (default 1024 MB).  Bigger regions let fewer trees
         // spill to the second pass, but the lanes' regions then lie far apart and the copies into and
         // out of them miss the TLB page by page: the gather of config #5's 100k staged trees took
         // 34 us from 4 GiB of regions, 143 us from 8 GiB and 298 us from 16 GiB
-        const char* sg = getenv("KETO_EXPAND_STAGE_MB");
-        const uint64_t budget = (sg ? (uint64_t)std::max(16, atoi(sg)) : 1024ull) << 17;
+        const uint64_t budget = (uint64_t)std::max(16, env_int("KETO_EXPAND_STAGE_MB", 1024)) << 17;
         stage_cap = std::min<uint64_t>(16384, std::max<uint64_t>(64, budget / p.slots[0]));
-        if (se && atoi(se) > 1) stage_cap = (uint64_t)atoi(se);            // tests: small regions spill
+        if (se > 1) stage_cap = (uint64_t)se;            // tests: small regions spill
         // a tree past its region goes on in an overflow chunk of KETO_EXPAND_OVF_CHUNK nodes (default
         // 256K) from a pool of KETO_EXPAND_OVF_NODES (default a quarter of the regions' nodes, at
         // least 4 chunks, at most 32M nodes = 256 MB; 0: none, such trees are filled by the second pass)
-        const char* oc = getenv("KETO_EXPAND_OVF_CHUNK");
-        const char* on = getenv("KETO_EXPAND_OVF_NODES");
-        ovf_chunk = oc ? (uint64_t)std::max(1, atoi(oc)) : 262144ull;
-        ovf_cap = on ? (uint64_t)std::max(0ll, atoll(on))
+        ovf_chunk = (uint64_t)std::max(1, env_int("KETO_EXPAND_OVF_CHUNK", 262144));
+        ovf_cap = env_set("KETO_EXPAND_OVF_NODES") ? (uint64_t)std::max(0ll, env_ll("KETO_EXPAND_OVF_NODES", 0))
                      : std::min<uint64_t>(32ull << 20, std::max<uint64_t>(4 * ovf_chunk, stage_cap * p.slots[0] / 4));
         ovf_cap -= ovf_cap % ovf_chunk;
         ovf_base = stage_cap * p.slots[0];
@@ -5508,8 +5452,7 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
         HIP_OK(hipMemsetAsync(D.ex_seg, 0, 16, st));
     }
     // the id-run queues of tier 0's lanes (RUNS_PER_LANE entries each) | runs queued per lane
-    const char* ri = getenv("KETO_EXPAND_RUN_INLINE");
-    const uint32_t run_inline = ri ? (uint32_t)atoi(ri) : RUN_INLINE_DEFAULT;
+    const uint32_t run_inline = (uint32_t)env_int("KETO_EXPAND_RUN_INLINE", (int)RUN_INLINE_DEFAULT);
     if (D.ex_runs_cap < p.slots[0]) {
         if (D.ex_runs) (void)hipFree(D.ex_runs);
         D.ex_runs = nullptr;
@@ -5524,8 +5467,8 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     // pieces are queued again); a queue that is full anyway copies the run in place
     auto ensure_big = [&](uint64_t nodes) {
         uint32_t cap = (uint32_t)std::min<uint64_t>(2 * nodes / BIG_RUN + 4096, 1u << 26);
-        if (const char* bc = getenv("KETO_EXPAND_BIG_CAP")) {          // tests: a queue that fills
-            cap = std::max(1, atoi(bc));
+        if (env_set("KETO_EXPAND_BIG_CAP")) {          // tests: a queue that fills
+            cap = std::max(1, env_int("KETO_EXPAND_BIG_CAP", 1));
             if (D.ex_big_cap != cap && D.ex_big) {
                 (void)hipFree(D.ex_big);
                 D.ex_big = nullptr;
@@ -5543,11 +5486,10 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
         if (!D.ex_ev[e]) HIP_OK(hipEventCreate(&D.ex_ev[e]));
     // tier 0 walks with expand_sm (one access per iteration, frames in LDS) when the saved frames
     // fit its LDS stack; KETO_EXPAND_SM=0: expand_one (tooling)
-    const char* sme = getenv("KETO_EXPAND_SM");
-    const bool sm = gmd <= SM_FRAMES && !(sme && atoi(sme) == 0);
+    const bool sm = gmd <= SM_FRAMES && !env_is("KETO_EXPAND_SM", 0);
     // KETO_EXPAND_SPREAD=2|4 (A/B): tier 0's trees on 64 / spread lanes per wave
-    const char* spe = getenv("KETO_EXPAND_SPREAD");
-    const uint32_t spread = spe && (atoi(spe) == 2 || atoi(spe) == 4) ? (uint32_t)atoi(spe) : 1u;
+    const int spe = env_int("KETO_EXPAND_SPREAD", 1);
+    const uint32_t spread = spe == 2 || spe == 4 ? (uint32_t)spe : 1u;
     // (the batch timing sums the passes' tiers: keto_last_batch_timing after an expand)
     auto launch_pass = [&](bool fill, const ExpandOut& eo) {
         run_tiers(D, D.ews, n, p, st,
@@ -5611,8 +5553,7 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     };
     // grids of the grid-stride copy kernels (a wave per lane / per root): capped, so that a launch is
     // not mostly the dispatch of waves with nothing to copy; KETO_EXPAND_COPY_BLOCKS overrides (tuning)
-    const char* cbe = getenv("KETO_EXPAND_COPY_BLOCKS");
-    const uint32_t cb_cap = cbe ? (uint32_t)std::max(1, atoi(cbe)) : 16384u;
+    const uint32_t cb_cap = (uint32_t)std::max(1, env_int("KETO_EXPAND_COPY_BLOCKS", 16384));
     auto copy_blocks = [&](uint64_t want) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, cb_cap)); };
     uint32_t* d_nbig = nullptr;
     auto copy_queued = [&]() {
@@ -5666,14 +5607,12 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     // pass 1: count (and stage), then the staged trees' queued id runs
     HIP_OK(hipMemsetAsync(dstage, 0xFF, (uint64_t)n * sizeof(uint64_t), st));
     if (staged) big_queue(stage_cap * p.slots[0]);
-    const uint32_t blind = S.n_poisoned_rows == 0 && getenv("KETO_EXPAND_LOAD_LEAVES") == nullptr;
-    const char* pfe = getenv("KETO_EXPAND_PREFETCH");
-    const uint32_t pf = pfe ? (uint32_t)(atoi(pfe) != 0) : 1u;
-    const char* ebe = getenv("KETO_EXPAND_EDGE_BLOCKS");
-    const uint32_t eb = ebe ? (uint32_t)(atoi(ebe) != 0) : 1u;
+    const uint32_t blind = S.n_poisoned_rows == 0 && !env_set("KETO_EXPAND_LOAD_LEAVES");
+    const uint32_t pf = (uint32_t)(env_int("KETO_EXPAND_PREFETCH", 1) != 0);
+    const uint32_t eb = (uint32_t)(env_int("KETO_EXPAND_EDGE_BLOCKS", 1) != 0);
     // KETO_EXPAND_CLOCKS=1 (tooling): the first pass's per-root walk times, summarized on stderr
     uint32_t* d_clocks = nullptr;
-    if (getenv("KETO_EXPAND_CLOCKS")) {
+    if (env_set("KETO_EXPAND_CLOCKS")) {
         d_clocks = dmalloc<uint32_t>(2ull * n, acc);
         HIP_OK(hipMemsetAsync(d_clocks, 0, 2ull * n * sizeof(uint32_t), st));
     }
@@ -5792,8 +5731,8 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     // (a wave each) instead of one 16-lane group, whose copy of the biggest trees set the gather's
     // time (KETO_EXPAND_GATHER_BIG: the threshold, 0 = every single-piece tree in the gather)
     constexpr uint64_t GPIECE = 512;
-    const char* gbe = getenv("KETO_EXPAND_GATHER_BIG");
-    const uint64_t gbig = gbe ? (atoll(gbe) > 0 ? (uint64_t)atoll(gbe) : ~0ull) : 256u;
+    const long long gbe = env_ll("KETO_EXPAND_GATHER_BIG", 256);
+    const uint64_t gbig = gbe > 0 ? (uint64_t)gbe : ~0ull;
     if (staged)
         hipLaunchKernelGGL(gather_staged, dim3(copy_blocks((n + 15) / 16)), dim3(256), 0, st,
                            D.ex_nodes, D.ex_stage, dstage, doff, n, fuse ? D.unit_row : nullptr, (uint32_t)S.n_units,

@@ -30,18 +30,12 @@
 #include <cstring>
 #include <vector>
 
+#include "hip_check.hpp"
 #include "json_runs.hpp"
 #include "parallel.hpp"
 #include "snapshot.hpp"
 
 namespace keto {
-
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t err__ = (x);                                                                     \
-        if (err__ != hipSuccess)                                                                    \
-            throw Error{KETO_E_HIP, std::string(#x) + ": " + hipGetErrorString(err__)};             \
-    } while (0)
 
 namespace {
 

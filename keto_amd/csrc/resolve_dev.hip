@@ -29,19 +29,13 @@
 #include <memory>
 #include <mutex>
 
+#include "hip_check.hpp"
 #include "parallel.hpp"
 #include "snapshot.hpp"
 
 namespace keto {
 
 namespace {
-
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t err__ = (x);                                                                     \
-        if (err__ != hipSuccess)                                                                    \
-            throw Error{KETO_E_HIP, std::string(#x) + ": " + hipGetErrorString(err__)};             \
-    } while (0)
 
 struct RBuf {                      // grow-only device buffer
     void* p = nullptr;

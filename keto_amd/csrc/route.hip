@@ -17,14 +17,8 @@
 // output of keto_row_owner uploaded once.
 #include <hip/hip_runtime.h>
 
+#include "hip_check.hpp"
 #include "snapshot.hpp"
-
-#define HIP_OK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t err__ = (x);                                                                     \
-        if (err__ != hipSuccess)                                                                    \
-            throw Error{KETO_E_HIP, std::string(#x) + ": " + hipGetErrorString(err__)};             \
-    } while (0)
 
 namespace keto {
 namespace {

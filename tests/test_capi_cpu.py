@@ -190,16 +190,56 @@ def test_string_table_grows_across_chunks(tmp_path):
     assert s.resolve_checks([("docs", "n0_0", "view", ("id", "late"), 0)])[0]["target"][0] == st["n_strings"]
 
 
-def test_engine_build_id_keys_traffic_profiles():
-    """The PMC traffic profiles bench.py reports as `roofline.traffic` are keyed on engine.hip and its
-    compile flags (keto_amd/build.py SOURCE_FLAGS): the key changes with the flags, and a committed
-    profile exists for the build as it stands, so the round's bench line carries measured traffic."""
+def test_engine_build_id_keys_traffic_profiles(tmp_path, monkeypatch):
+    """The PMC traffic profiles bench.py reports as `roofline.traffic` are keyed on what the tier-0
+    check kernel is compiled from: engine.hip, the csrc headers it includes (hip_check.hpp,
+    snapshot.hpp) and its compile flags (keto_amd/build.py SOURCE_FLAGS).  The key changes with the
+    flags, and a committed profile exists for the build as it stands, so the round's bench line
+    carries measured traffic.  A source engine.hip does not include is not part of the key."""
     import glob
     import hashlib
     import json
+    import shutil
     from keto_amd import build
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(build.CSRC, "engine.hip"), "rb").read()
     assert build.engine_build_id() != hashlib.sha256(src).hexdigest() or not build.SOURCE_FLAGS.get("engine.hip")
     keys = [json.load(open(p)).get("engine_sha256") for p in glob.glob(os.path.join(root, "profiles", "*_traffic.json"))]
     assert build.engine_build_id() in keys
+    # on a scratch copy of the sources: a byte more in engine.hip or in a header it includes changes
+    # the key, a byte more in another unit or in a header it does not include keeps it
+    want = build.engine_build_id()
+    scratch = str(tmp_path / "csrc")
+    shutil.copytree(build.CSRC, scratch, ignore=shutil.ignore_patterns("*.o"))
+    monkeypatch.setattr(build, "CSRC", scratch)
+    assert build.engine_build_id() == want
+    for name, same in (("engine.hip", False), ("hip_check.hpp", False), ("snapshot.hpp", False),
+                       ("route.hip", True), ("migrate.hip", True), ("parallel.hpp", True)):
+        path = os.path.join(scratch, name)
+        before = open(path, "rb").read()
+        with open(path, "ab") as f:
+            f.write(b"\n")
+        assert (build.engine_build_id() == want) == same, name
+        with open(path, "wb") as f:
+            f.write(before)
+    assert build.engine_build_id() == want
+
+
+def test_check_kernel_names(monkeypatch):
+    """keto_check_kernel_name reads no device: the tier-0 instance a depth and the environment pick,
+    by name (the name column of engine.hip's T0_TABLE)."""
+    wave = "keto::check_wave_kernel<%s, false, false>"
+    variants = ["4, false, 4, 16", "4, false, 4, 8", "4, false, 12, 4", "4, false, 8, 8", "4, false, 8, 6",
+                "4, false, 12, 6", "4, false, 6, 8", "4, true, 8, 8"]
+    name = keto_amd.Snapshot.check_kernel_name
+    for k in ("KETO_T0", "KETO_DEEP_WAVE"):
+        monkeypatch.delenv(k, raising=False)
+    assert name(5) == wave % variants[3]
+    for v, args in enumerate(variants):
+        monkeypatch.setenv("KETO_T0", str(v))
+        assert name(5) == wave % args
+    monkeypatch.delenv("KETO_T0")
+    assert name(9) == wave % "8, false, 8, 8"
+    assert name(10) == "keto::check_kernel<keto::GlobalStack, false, 0>"
+    monkeypatch.setenv("KETO_DEEP_WAVE", "1")
+    assert name(10) == "keto::deep_wave_kernel<8, 8, false>"

@@ -9,7 +9,8 @@ PMC passes).  Correction (calibrated with tools/calib.hip on an MI355X, profiles
 FETCH_SIZE tallies 64 B per L2 miss while every miss is a 128-B DRAM read (TCC_EA0_RDREQ_128B =
 TCC_EA0_RDREQ), for streaming reads and for random 4-16 B gathers alike, so read bytes =
 2 x FETCH_SIZE x 1024; WRITE_SIZE x 1024 is taken as is.
-The json carries the sha256 of engine.hip and its compile flags, so bench.py only uses it for the kernel it was measured on.
+The json carries the sha256 of engine.hip, the csrc headers it includes and its compile flags, so bench.py
+only uses it for the kernel it was measured on.
 """
 import collections
 import csv
@@ -25,7 +26,7 @@ def engine_sha():
     spec = importlib.util.spec_from_file_location("_keto_build", os.path.join(ROOT, "keto_amd", "build.py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
-    return m.engine_build_id()   # engine.hip and its compile flags
+    return m.engine_build_id()   # engine.hip, the csrc headers it includes, its compile flags
 
 
 def pmc(path, counter, kernel):
