@@ -156,10 +156,13 @@ def test_random_expand_json_all_equals_per_tree(seed):
 def test_deep_chain_tree_json():
     """A 2,500-level tree (a chain of nested groups expanded with max-depth 3000): the JSON encoders
     are iterative, so a tree as deep as the max-depth allows encodes without exhausting the host
-    stack; the text equals the chain's expected JSON."""
+    stack; the text equals the chain's expected JSON, and the three protobuf encoders give the
+    protobuf runtime's bytes of that tree."""
+    import json
     import sys
     from keto_amd.capi import EXPAND_TREE
     from oracle.oracle_sql import RelationTuple, SubjectID, SubjectSet
+    from tests.proto_util import tree_json_to_proto
     k = 2500
     ns = [(1, "n")]
     tuples = [RelationTuple("n", f"g{i}", "m", SubjectSet("n", f"g{i + 1}", "m")) for i in range(k - 1)]
@@ -183,10 +186,13 @@ def test_deep_chain_tree_json():
         (st, _, pb), = snap.expand_batch([(("set", "n", "g0", "m"), 3000)], 3000, want_proto=True)
         _, host = snap.expand_batch([(("set", "n", "g0", "m"), 3000)], 3000, proto_all="host")
         _, dev = snap.expand_batch([(("set", "n", "g0", "m"), 3000)], 3000, proto_all="device")
+        # the protobuf runtime's bytes of the same tree (it serializes this deep; it would not parse)
+        ref = tree_json_to_proto(json.loads(want))
     finally:
         sys.setrecursionlimit(old)
     assert st == EXPAND_TREE and len(pb) > 0
     assert host[0] == pb and dev[0] == pb
+    assert pb == ref
 
 
 @pytest.mark.parametrize("seed", range(2000, 2060))
