@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define KETO_ABI_VERSION 7
+#define KETO_ABI_VERSION 8
 /* The largest arena one snapshot (a replica) or one partition part takes on a device: handles are
  * 32-bit; below 2^31 a count of 16-byte units (subject-set targets, and the root rows of the first
  * 32 GiB), above it a count of 32-, 64- or 128-byte units of the root rows past 32 GiB (arenas past
@@ -585,6 +585,41 @@ int64_t keto_tree_proto_all_device(keto_snapshot* s, const keto_tree_arena* a, u
  * Fails like keto_tree_proto_all_device on a host-only snapshot (device = -1). */
 int64_t keto_tree_json_all_device(keto_snapshot* s, const keto_tree_arena* a, char* buf, uint64_t cap,
                                   uint64_t* offsets);
+
+/* Expand and encode in one call, the node arena never leaving the device: roots in, response bodies
+ * out.  Replaces, for a batch, what the reference's Expand handlers do per request: BuildTree and
+ * then h.d.Writer().Write(tree) via Tree.MarshalJSON (REST, internal/expand/handler.go:77-91,
+ * internal/expand/tree.go:156-163), or BuildTree and then tree.ToProto() (gRPC,
+ * internal/expand/handler.go:93-104, internal/expand/tree.go:165-188).  The bytes, offsets and
+ * statuses are exactly those of keto_expand_batch[_ids] followed by keto_tree_status and
+ * keto_tree_proto_all (KETO_ENC_PROTO) / keto_tree_json_all (KETO_ENC_JSON) on the same requests:
+ * JSON has "null" for a nil tree and nothing for KETO_EXPAND_NOT_FOUND / KETO_EXPAND_UNDECIDED roots,
+ * protobuf nothing for all three.  Against keto_expand_batch + a sizing and a filling
+ * keto_tree_*_all_device call it saves the arena's D2H and H2D copies and the second run of the size
+ * kernels: the trees are expanded into the snapshot's device buffers, their set handles and
+ * batch-local wildcard rows turned into row ids by kernels there, sized once, written, and copied by
+ * one DMA into a block of the library's pinned pool, which the result owns.
+ * The result holds no reference to the snapshot: it stays readable after keto_snapshot_apply and
+ * keto_snapshot_release, until keto_encoded_free.  n = 0 gives count 0, offsets {0} and total 0.
+ * Errors: an unknown encoding is KETO_E_INVALID; a host-only snapshot (device = -1) and a root owned
+ * by another shared-rows part fail as in keto_expand_batch (KETO_E_HIP / KETO_E_INVALID); a migrating
+ * part (KETO_PART_MIGRATE, n_parts > 1) is KETO_E_INVALID -- it translates the rows it pulls from
+ * other parts on the host: use keto_expand_batch and an encoder there.  keto_last_batch_timing
+ * reports the expand passes as after keto_expand_batch. */
+#define KETO_ENC_PROTO 0   /* acl.SubjectTree bytes, as keto_tree_proto_all */
+#define KETO_ENC_JSON  1   /* Tree.MarshalJSON text, as keto_tree_json_all  */
+typedef struct keto_encoded keto_encoded;
+int keto_expand_encode_batch(keto_snapshot* s, const keto_expand_req* reqs, uint32_t n, int32_t global_max_depth,
+                             uint32_t encoding, keto_encoded** out);
+/* Same with pre-resolved roots, as keto_expand_batch_ids takes them. */
+int keto_expand_encode_batch_ids(keto_snapshot* s, const uint32_t* roots, const int32_t* max_depth, uint32_t n,
+                                 int32_t global_max_depth, uint32_t encoding, keto_encoded** out);
+void keto_encoded_free(keto_encoded* e);                               /* NULL is fine */
+uint32_t keto_encoded_count(const keto_encoded* e);                    /* n */
+/* the bytes of every tree, back to back (NULL when the total is 0); *total_out = their count */
+const uint8_t* keto_encoded_bytes(const keto_encoded* e, uint64_t* total_out);
+const uint64_t* keto_encoded_offsets(const keto_encoded* e);           /* n + 1; tree i = bytes[off[i], off[i+1]) */
+const uint8_t* keto_encoded_status(const keto_encoded* e);             /* n x KETO_EXPAND_* */
 
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,

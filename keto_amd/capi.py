@@ -16,7 +16,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KETO_LIB") or os.path.join(HERE, "libketo_mi355x.so")   # KETO_LIB: tuning builds
 
-KETO_ABI_VERSION = 7          # include/keto_mi355x.h KETO_ABI_VERSION: load() refuses any other library
+KETO_ABI_VERSION = 8          # include/keto_mi355x.h KETO_ABI_VERSION: load() refuses any other library
 KETO_OK = 0
 E_REBUILD = -6
 CHECK_OK, CHECK_UNKNOWN_NAMESPACE, CHECK_UNDECIDED = 0, 1, 2
@@ -42,7 +42,11 @@ EXPORTS = [
     "keto_check_batch_routed_packed",
     "keto_comm_close_filters", "keto_comm_init_local", "keto_snapshot_clone", "keto_check_batch_packed",
     "keto_snapshot_save", "keto_snapshot_load", "keto_expand_batch_routed",
+    "keto_expand_encode_batch", "keto_expand_encode_batch_ids", "keto_encoded_free", "keto_encoded_count",
+    "keto_encoded_bytes", "keto_encoded_offsets", "keto_encoded_status",
 ]
+ENC_PROTO, ENC_JSON = 0, 1
+ENCODINGS = {"proto": ENC_PROTO, "json": ENC_JSON}
 PART_SHARED, PART_MIGRATE = 0, 1
 MIG_MAX_PARTS = 30
 FILTER_WORDS = 22
@@ -198,6 +202,17 @@ def load():
     lib.keto_route_work_bytes.restype = C.c_uint64
     lib.keto_snapshot_version.restype = C.c_uint64
     lib.keto_part_stubs.restype = C.c_int64
+    if hasattr(lib, "keto_encoded_free"):
+        lib.keto_encoded_free.restype = None
+        lib.keto_encoded_free.argtypes = [C.c_void_p]
+        lib.keto_encoded_count.restype = C.c_uint32
+        lib.keto_encoded_count.argtypes = [C.c_void_p]
+        lib.keto_encoded_bytes.restype = C.c_void_p
+        lib.keto_encoded_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.keto_encoded_offsets.restype = C.c_void_p
+        lib.keto_encoded_offsets.argtypes = [C.c_void_p]
+        lib.keto_encoded_status.restype = C.c_void_p
+        lib.keto_encoded_status.argtypes = [C.c_void_p]
     lib.keto_route_work_bytes.argtypes = [C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
@@ -690,6 +705,46 @@ class Snapshot:
         finally:
             self.lib.keto_tree_arena_free(a)
         return status, offs, blob, t1 - t0, t_enc
+
+    @staticmethod
+    def _encoding(encoding) -> int:
+        return ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+
+    def _encoded_result(self, e):
+        """(status[n], offsets[n+1], bytes) copied out of a keto_encoded handle, which is freed here."""
+        try:
+            n = self.lib.keto_encoded_count(e)
+            total = C.c_uint64()
+            p = self.lib.keto_encoded_bytes(e, C.byref(total))
+            status = np.frombuffer(C.string_at(self.lib.keto_encoded_status(e), n), dtype=np.uint8).astype(np.int32)
+            offs = np.frombuffer(C.string_at(self.lib.keto_encoded_offsets(e), 8 * (n + 1)), dtype=np.uint64).copy()
+            blob = C.string_at(p, total.value) if total.value else b""
+        finally:
+            self.lib.keto_encoded_free(e)
+        return status, offs, blob
+
+    def expand_batch_encoded(self, reqs, global_max_depth=5, encoding="json"):
+        """keto_expand_encode_batch: reqs as in expand_batch -> (status[n], offsets[n+1], bytes), every
+        tree's Tree.MarshalJSON text ("json") or acl.SubjectTree bytes ("proto") back to back, expanded
+        and encoded on the device."""
+        keep = _Keep()
+        arr = self._expand_reqs(keep, reqs)
+        e = C.c_void_p()
+        _check(self.lib.keto_expand_encode_batch(self.h, arr, C.c_uint32(len(reqs)), C.c_int32(global_max_depth),
+                                                 C.c_uint32(self._encoding(encoding)), C.byref(e)))
+        return self._encoded_result(e)
+
+    def expand_batch_ids_encoded(self, roots: np.ndarray, depths: np.ndarray, global_max_depth=5, encoding="json"):
+        """keto_expand_encode_batch_ids: pre-resolved roots as in expand_batch_ids -> (status[n],
+        offsets[n+1], bytes)."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        depths = np.ascontiguousarray(depths, dtype=np.int32)
+        e = C.c_void_p()
+        _check(self.lib.keto_expand_encode_batch_ids(self.h, roots.ctypes.data_as(C.c_void_p),
+                                                     depths.ctypes.data_as(C.c_void_p), C.c_uint32(len(roots)),
+                                                     C.c_int32(global_max_depth), C.c_uint32(self._encoding(encoding)),
+                                                     C.byref(e)))
+        return self._encoded_result(e)
 
     def _proto_all(self, a, n, device=False):
         """(offsets[n+1], blob, seconds of the sizing + filling calls, as a caller pays them) of

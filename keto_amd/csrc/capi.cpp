@@ -898,7 +898,7 @@ namespace keto {
 // keto_expand_batch's body (the caller holds the snapshot's lock shared); skip[i] != 0: request i is
 // answered elsewhere (comm.cpp routes it to the part owning its root row) and gets an empty slot
 void expand_named(Snapshot& S, const keto_expand_req* reqs, uint32_t n, int32_t global_max_depth, keto_tree_arena& A,
-                  const uint8_t* skip) {
+                  const uint8_t* skip, ExpandOnDevice* keep) {
     keto_tree_arena* a = &A;
     Overlay ov;
     ov.base = S.n_rows();
@@ -953,9 +953,30 @@ void expand_named(Snapshot& S, const keto_expand_req* reqs, uint32_t n, int32_t 
         }
     }
     a->ov_keys = ov.keys;
-    device_expand(S, root, flags, vid, depth, global_max_depth, &ov, a->r, &remote, &rrow);
+    device_expand(S, root, flags, vid, depth, global_max_depth, &ov, a->r, &remote, &rrow, keep);
     for (uint32_t i = 0; i < n; ++i)
         if (not_found[i]) a->r.status[i] = KETO_EXPAND_NOT_FOUND;
+}
+
+// keto_expand_batch_ids' resolution of its roots (row ids -> handles), shared with the encoding form
+void expand_ids(Snapshot& S, const uint32_t* roots, const int32_t* max_depth, uint32_t n, int32_t global_max_depth,
+                keto_tree_arena& A, ExpandOnDevice* keep) {
+    A.extra_base = (uint32_t)S.strs.size();
+    std::vector<uint32_t> root(n), flags(n), vid(n, 0), rrow(n, KETO_NO_ROW);
+    std::vector<int32_t> depth(max_depth, max_depth + n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool set = (roots[i] & EDGE_SET) != 0;
+        root[i] = roots[i] & EDGE_VAL;
+        flags[i] = set ? 1u : 0u;
+        if (set) {
+            if (root[i] >= S.n_rows()) throw Error{KETO_E_INVALID, "root row out of range"};
+            if (!S.present(root[i])) throw Error{KETO_E_INVALID, "expand root is owned by another part"};
+            vid[i] = S.vid_of_row(root[i]);
+            rrow[i] = root[i];
+            root[i] = S.handle(root[i]);
+        }
+    }
+    device_expand(S, root, flags, vid, depth, global_max_depth, nullptr, A.r, nullptr, &rrow, keep);
 }
 }  // namespace keto
 }  // extern "C++"
@@ -979,24 +1000,8 @@ int keto_expand_batch_ids(keto_snapshot* h, const uint32_t* roots, const int32_t
         if (!h || !out || (n && (!roots || !max_depth))) throw Error{KETO_E_INVALID, "NULL argument"};
         std::shared_lock<RwGate> lk(h->s->rw);
         *out = nullptr;
-        Snapshot& S = *h->s;
         auto a = std::make_unique<keto_tree_arena>();
-        a->extra_base = (uint32_t)S.strs.size();
-        std::vector<uint32_t> root(n), flags(n), vid(n, 0), rrow(n, KETO_NO_ROW);
-        std::vector<int32_t> depth(max_depth, max_depth + n);
-        for (uint32_t i = 0; i < n; ++i) {
-            const bool set = (roots[i] & EDGE_SET) != 0;
-            root[i] = roots[i] & EDGE_VAL;
-            flags[i] = set ? 1u : 0u;
-            if (set) {
-                if (root[i] >= S.n_rows()) throw Error{KETO_E_INVALID, "root row out of range"};
-                if (!S.present(root[i])) throw Error{KETO_E_INVALID, "expand root is owned by another part"};
-                vid[i] = S.vid_of_row(root[i]);
-                rrow[i] = root[i];
-                root[i] = S.handle(root[i]);
-            }
-        }
-        device_expand(S, root, flags, vid, depth, global_max_depth, nullptr, a->r, nullptr, &rrow);
+        expand_ids(*h->s, roots, max_depth, n, global_max_depth, *a, nullptr);
         *out = a.release();
         return KETO_OK;
     });
@@ -1198,6 +1203,99 @@ int64_t keto_tree_json_all_device(keto_snapshot* h, const keto_tree_arena* a, ch
                                          a->extra_base, a->extra, reinterpret_cast<uint8_t*>(buf), cap, offsets);
     });
 }
+
+// ---- keto_expand_encode_batch: expand and encode without the node arena leaving the device
+struct keto_encoded {
+    std::vector<uint8_t> status;
+    std::vector<uint64_t> offsets;          // n + 1
+    uint8_t* bytes = nullptr;               // a block of the pinned pool (pinned_take), or NULL (total 0)
+    uint64_t total = 0;
+    ~keto_encoded() { pinned_give(bytes); }
+};
+
+extern "C++" {
+// Lock order: rw shared -> D.mu (device_expand takes it and hands it over in `keep`) -> S.mu (the
+// encoder).  D.mu is held until the encoder has read the arena out of the device state's buffers,
+// so another thread's expand on the snapshot cannot overwrite it; device_expand drains its stream
+// before it returns, so the encoder's stream-0 work follows the arena's writes.  Nothing takes them
+// the other way round: the holders of S.mu (the encoders in proto.hip, mig_begin / mig_round) call
+// nothing that takes D.mu, and apply takes D.mu under rw exclusive, which this call excludes.
+template <class Expand>
+int expand_encode(keto_snapshot* h, uint32_t encoding, keto_encoded** out, Expand expand) {
+    if (encoding != KETO_ENC_PROTO && encoding != KETO_ENC_JSON)
+        throw Error{KETO_E_INVALID, "unknown encoding " + std::to_string(encoding)};
+    *out = nullptr;
+    // KETO_EXPAND_TRACE=1: the call's two halves on stderr, next to their own phase lines (tooling)
+    const bool trace = getenv("KETO_EXPAND_TRACE") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::shared_lock<RwGate> rlk(h->s->rw);        // strings / row keys (before D.mu and S.mu)
+    Snapshot& S = *h->s;
+    keto_tree_arena a;                              // the call's overlay keys, extra strings, statuses, offsets
+    ExpandOnDevice keep;                            // (dropped, with D.mu, before rw)
+    expand(S, a, &keep);
+    const auto t1 = std::chrono::steady_clock::now();
+    const uint32_t n = (uint32_t)a.r.status.size();
+    auto e = std::make_unique<keto_encoded>();
+    e->status = a.r.status;
+    e->offsets.assign(n + 1ull, 0);
+    if (n == 0) {
+    } else if (encoding == KETO_ENC_PROTO) {
+        e->total = device_tree_proto_resident(S, keep.arena, a.r.offset.data(), n, a.ov_base, a.ov_keys, a.extra_base,
+                                              a.extra, &e->bytes, e->offsets.data());
+    } else {
+        // nil trees ("null") as keto_tree_json_all_device marks them, from the final statuses
+        // (KETO_EXPAND_NOT_FOUND included, which expand_named sets after the expand)
+        std::vector<uint8_t> nil(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const int st = a.r.status[i];
+            nil[i] = st != KETO_EXPAND_TREE && st != KETO_EXPAND_NOT_FOUND && st != KETO_EXPAND_UNDECIDED;
+        }
+        e->total = device_tree_json_resident(S, keep.arena, a.r.offset.data(), nil.data(), n, a.ov_base, a.ov_keys,
+                                             a.extra_base, a.extra, &e->bytes, e->offsets.data());
+    }
+    if (trace) {
+        const auto t2 = std::chrono::steady_clock::now();
+        fprintf(stderr, "[encoded] expand %8.3f ms, encode %8.3f ms (%llu bytes)\n",
+                std::chrono::duration<double, std::milli>(t1 - t0).count(),
+                std::chrono::duration<double, std::milli>(t2 - t1).count(), (unsigned long long)e->total);
+    }
+    *out = e.release();
+    return KETO_OK;
+}
+}  // extern "C++"
+
+int keto_expand_encode_batch(keto_snapshot* h, const keto_expand_req* reqs, uint32_t n, int32_t global_max_depth,
+                             uint32_t encoding, keto_encoded** out) {
+    return guarded([&] {
+        if (!h || !out || (n && !reqs)) throw Error{KETO_E_INVALID, "NULL argument"};
+        return expand_encode(h, encoding, out, [&](Snapshot& S, keto_tree_arena& a, ExpandOnDevice* keep) {
+            expand_named(S, reqs, n, global_max_depth, a, nullptr, keep);
+        });
+    });
+}
+
+int keto_expand_encode_batch_ids(keto_snapshot* h, const uint32_t* roots, const int32_t* max_depth, uint32_t n,
+                                 int32_t global_max_depth, uint32_t encoding, keto_encoded** out) {
+    return guarded([&] {
+        if (!h || !out || (n && (!roots || !max_depth))) throw Error{KETO_E_INVALID, "NULL argument"};
+        return expand_encode(h, encoding, out, [&](Snapshot& S, keto_tree_arena& a, ExpandOnDevice* keep) {
+            expand_ids(S, roots, max_depth, n, global_max_depth, a, keep);
+        });
+    });
+}
+
+void keto_encoded_free(keto_encoded* e) { delete e; }
+
+uint32_t keto_encoded_count(const keto_encoded* e) { return e ? (uint32_t)e->status.size() : 0; }
+
+const uint8_t* keto_encoded_bytes(const keto_encoded* e, uint64_t* total_out) {
+    if (total_out) *total_out = e ? e->total : 0;
+    return e ? e->bytes : nullptr;
+}
+
+const uint64_t* keto_encoded_offsets(const keto_encoded* e) { return e ? e->offsets.data() : nullptr; }
+
+const uint8_t* keto_encoded_status(const keto_encoded* e) { return e ? e->status.data() : nullptr; }
 
 int64_t keto_subject_fields(const keto_snapshot* h, const keto_tree_arena* a, const uint32_t* subjects, uint64_t n,
                             char* buf, uint64_t cap, uint32_t* lens_out) {

@@ -62,8 +62,9 @@ void check_named(Snapshot& S, const keto_check_req* reqs, uint32_t n, int32_t gl
                  uint8_t* status_out);
 
 // keto_expand_batch's body, the caller holding the snapshot's lock shared (capi.cpp); skip[i] != 0:
-// request i is answered by another part (an empty slot here)
+// request i is answered by another part (an empty slot here); keep: device_expand's form that
+// leaves the node arena on the device (a.r.nodes stays empty)
 void expand_named(Snapshot& S, const keto_expand_req* reqs, uint32_t n, int32_t global_max_depth, keto_tree_arena& a,
-                  const uint8_t* skip);
+                  const uint8_t* skip, ExpandOnDevice* keep = nullptr);
 
 }  // namespace keto

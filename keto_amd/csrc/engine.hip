@@ -5271,6 +5271,52 @@ __global__ void __launch_bounds__(256) handles_to_rows(keto_tree_node* __restric
     nodes[i].subject = EDGE_SET | rows[lo];
 }
 
+// An arena that stays on the device (device_expand's `keep` form) gets the two fix-ups the host
+// does after the D2H otherwise, as kernels (grid-stride; a thread's stores are a node's subject word).
+// ov_unit: the call's overlay rows' arena units, ascending (Overlay::unit), n_ov of them; the row id
+// of the one at unit u is ov_base + its index.
+__device__ inline uint32_t ov_unit_index(const uint32_t* __restrict__ ov_unit, uint32_t n_ov, uint32_t u) {
+    uint32_t lo = 0, hi = n_ov;                    // first unit >= u (std::lower_bound)
+    while (lo < hi) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (ov_unit[m] < u) lo = m + 1;
+        else hi = m;
+    }
+    return lo;
+}
+// fix_high_roots (arenas with root rows past 2^31 units): a tree's root node lost its handle's bit
+// 31 to EDGE_SET, so it takes its row from the request (root_rows), or its overlay row id.  One
+// thread per tree.
+__global__ void __launch_bounds__(256) fix_high_roots(keto_tree_node* __restrict__ nodes, const uint64_t* __restrict__ offset,
+                                                      const ExpandReq* __restrict__ q, const uint32_t* __restrict__ root_rows,
+                                                      uint32_t n, uint64_t n_units, const uint32_t* __restrict__ ov_unit,
+                                                      uint32_t n_ov, uint32_t ov_base) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const ExpandReq rq = q[i];
+        const uint64_t b = offset[i];
+        if (!rq.flags || offset[i + 1] == b) continue;
+        if (rq.root >= EDGE_VAL && rq.root < n_units)
+            nodes[b].subject = EDGE_SET | root_rows[i];
+        else if (n_ov && rq.root >= n_units)
+            nodes[b].subject = EDGE_SET | (ov_base + ov_unit_index(ov_unit, n_ov, (uint32_t)(rq.root - n_units)));
+    }
+}
+// fix_overlay_rows (every other arena, when the call has overlay rows): the set nodes the handle
+// translation left alone (handles >= n_units: batch-local wildcard rows) take their overlay row id.
+// One thread per node.
+__global__ void __launch_bounds__(256) fix_overlay_rows(keto_tree_node* __restrict__ nodes, uint64_t n, uint32_t n_units,
+                                                        const uint32_t* __restrict__ ov_unit, uint32_t n_ov,
+                                                        uint32_t ov_base) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t x = nodes[i].subject;
+        if (!(x & EDGE_SET)) continue;
+        const uint32_t h = x & EDGE_VAL;
+        if (h < n_units) continue;
+        nodes[i].subject = EDGE_SET | (ov_base + ov_unit_index(ov_unit, n_ov, h - n_units));
+    }
+}
+
 // ---- the pinned block pool behind PinnedAlloc (snapshot.hpp); never destroyed, so an arena freed
 // late in process exit still finds it
 namespace {
@@ -5338,7 +5384,7 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
                    const std::vector<uint32_t>& root_vid_in, const std::vector<int32_t>& depth, int32_t gmd,
                    const Overlay* ovh, ExpandResult& out,
                    const std::vector<std::pair<uint32_t, uint32_t>>* remote_roots,
-                   const std::vector<uint32_t>* root_rows) {
+                   const std::vector<uint32_t>* root_rows, ExpandOnDevice* keep) {
     if (!S.dev) throw Error{KETO_E_HIP, "snapshot has no device copy"};
     if (S.n_units > (uint64_t)EDGE_VAL && (!root_rows || root_rows->size() != root_in.size()))
         throw Error{KETO_E_INVALID, "expand over an arena whose roots lie past 2^31 units needs the roots' row ids"};
@@ -5346,6 +5392,8 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     // tree needs from other parts are copied into the call's overlay (PullSet) from the host tables,
     // which every part holds whole
     const bool pulls = S.part_mode == PART_MIGRATE && S.n_parts > 1;
+    if (pulls && keep)           // (the pulled rows' identity slots are translated on the host, below)
+        throw Error{KETO_E_INVALID, "expand with device-side encoding is not available on a migrating part"};
     std::unique_ptr<PullSet> ps;
     std::vector<uint32_t> root_m, vid_m;
     if (pulls) {
@@ -5364,13 +5412,21 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     const std::vector<uint32_t>& root = pulls ? root_m : root_in;
     const std::vector<uint32_t>& root_vid = pulls ? vid_m : root_vid_in;
     DeviceState& D = *S.dev;
-    std::lock_guard<std::mutex> lk(D.mu);
+    std::unique_lock<std::mutex> lk(D.mu);
     HIP_OK(hipSetDevice(D.device));
     const uint32_t n = (uint32_t)root.size();
+    // the arena kept on the device: handed to the caller with D.mu (nothing overwrites it meanwhile)
+    auto keep_arena = [&](uint64_t total) {
+        keep->arena = ResidentArena{D.ex_nodes, total, reinterpret_cast<const uint64_t*>(D.ex_buf) + (n + 1)};
+        keep->hold = std::move(lk);
+    };
     out.status.assign(n, EXP_NIL);
     out.offset.assign(n + 1, 0);
     out.nodes.clear();
-    if (n == 0) return;
+    if (n == 0) {
+        if (keep) keep->hold = std::move(lk);          // (no arena: keep->arena stays empty)
+        return;
+    }
     if (gmd > 65535) gmd = 65535;
     hipStream_t st = D.stream;
     // KETO_EXPAND_TRACE=1: phase times on stderr (tooling)
@@ -5675,12 +5731,22 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     for (uint32_t i = 0; i < n; ++i) {
         out.offset[i + 1] = out.offset[i] + cnt[i];
         unstaged += (!staged || spos[i] == NOT_STAGED) && out.status[i] == EXP_TREE && cnt[i];
+        // The encoders over a kept arena take every node range as a tree's.  A root that is not
+        // EXP_TREE has none: expand_kernel stores count 0 for every other status it decides, and
+        // mark_undecided zeroes the count of the roots no tier decided.
+        if (keep && out.status[i] != EXP_TREE && cnt[i])
+            throw Error{KETO_E_HIP, "expand: root " + std::to_string(i) + " is no tree but has nodes"};
     }
     const uint64_t total = out.offset[n];
-    out.nodes.resize(total);
+    if (!keep) out.nodes.resize(total);
     lap("scan");
     if (total == 0) {
         D.last.tier_ms[0] += extra_ms;
+        if (keep) {                                   // (no nodes: the encoders still read the offsets)
+            HIP_OK(hipMemcpyAsync(doff, out.offset.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+            HIP_OK(hipStreamSynchronize(st));
+            keep_arena(0);
+        }
         return;
     }
     if (D.ex_nodes_cap < total) {
@@ -5812,15 +5878,40 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
     HIP_OK(hipGetLastError());
     const bool high_roots = S.n_units > (uint64_t)EDGE_VAL;
     lap("h2rows");
-    HIP_OK(hipMemcpyAsync(out.nodes.data(), D.ex_nodes, total * sizeof(keto_tree_node), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    lap("d2h");
-    // arenas with root rows past 2^31 units: a tree's root node lost its handle's bit 31 to EDGE_SET,
-    // so it takes its row from the request (overlay roots: below)
-    if (high_roots)
-        for (uint32_t i = 0; i < n; ++i)
-            if (root_flags[i] && out.offset[i + 1] > out.offset[i] && root[i] >= EDGE_VAL && root[i] < S.n_units)
-                out.nodes[out.offset[i]].subject = EDGE_SET | (*root_rows)[i];
+    if (keep) {
+        // the arena stays here: the host's fix-ups below (roots past 2^31 units, or else the overlay
+        // rows' handles) run as kernels on it, and the stream is drained, so that the encoders
+        // (stream 0) read a finished arena
+        const uint32_t n_ov = ovh ? (uint32_t)ovh->unit.size() : 0u;
+        std::unique_ptr<DevBuf<uint32_t>> d_ovu, d_rr;
+        if (n_ov && !ovh->empty()) {
+            d_ovu = std::make_unique<DevBuf<uint32_t>>(n_ov);
+            HIP_OK(hipMemcpyAsync(d_ovu->p, ovh->unit.data(), n_ov * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        }
+        if (high_roots) {
+            d_rr = std::make_unique<DevBuf<uint32_t>>(n);
+            HIP_OK(hipMemcpyAsync(d_rr->p, root_rows->data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(fix_high_roots, dim3(std::min<uint32_t>((n + 255) / 256, 4096)), dim3(256), 0, st, D.ex_nodes,
+                               doff, dq, d_rr->p, n, S.n_units, d_ovu ? d_ovu->p : nullptr, d_ovu ? n_ov : 0u,
+                               ovh ? ovh->base : 0u);
+        } else if (d_ovu) {
+            hipLaunchKernelGGL(fix_overlay_rows, dim3((unsigned)std::min<uint64_t>((total + 255) / 256, 16384)), dim3(256),
+                               0, st, D.ex_nodes, total, (uint32_t)S.n_units, d_ovu->p, n_ov, ovh->base);
+        }
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st));
+        lap("fixups");
+    } else {
+        HIP_OK(hipMemcpyAsync(out.nodes.data(), D.ex_nodes, total * sizeof(keto_tree_node), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        lap("d2h");
+        // arenas with root rows past 2^31 units: a tree's root node lost its handle's bit 31 to EDGE_SET,
+        // so it takes its row from the request (overlay roots: below)
+        if (high_roots)
+            for (uint32_t i = 0; i < n; ++i)
+                if (root_flags[i] && out.offset[i + 1] > out.offset[i] && root[i] >= EDGE_VAL && root[i] < S.n_units)
+                    out.nodes[out.offset[i]].subject = EDGE_SET | (*root_rows)[i];
+    }
     {
         float ms = 0;
         if (hipEventElapsedTime(&ms, D.ex_ev[2], D.ex_ev[3]) == hipSuccess) extra_ms += ms;
@@ -5835,6 +5926,10 @@ void device_expand(Snapshot& S, const std::vector<uint32_t>& root_in, const std:
             }
         fprintf(stderr, "[expand] %u of %u trees filled by the second pass (%llu nodes, the largest %llu); %u staged in two pieces\n",
                 unstaged, n, (unsigned long long)sum, (unsigned long long)big, n_split);
+    }
+    if (keep) {
+        keep_arena(total);
+        return;
     }
     // overlay handles -> ovh->base + overlay index (batch-local wildcard roots only); a migrating
     // part's identity slots -> the rows they name

@@ -720,12 +720,14 @@ static void d2h_staged(ProtoState& P, uint8_t* buf, const uint8_t* d_src, uint64
 namespace {
 struct Arena {
     Tables T;
-    keto_tree_node* nodes;
-    uint64_t* toff;
+    const keto_tree_node* nodes;
+    const uint64_t* toff;
 };
+// res != NULL: the nodes and tree offsets are on the device already (device_expand's arena, kept
+// there); only the call's tables are uploaded
 Arena upload_arena(Snapshot& S, ProtoState& P, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
                    uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
-                   const std::vector<std::string>& extra) {
+                   const std::vector<std::string>& extra, const ResidentArena* res) {
     ProtoWork& W = P.work;
     DevStrs& ex = W.ex;
     ex.upload((uint32_t)extra.size(), [&](uint32_t i) { return std::string_view(extra[i]); });
@@ -753,17 +755,40 @@ Arena upload_arena(Snapshot& S, ProtoState& P, const keto_tree_node* nodes, uint
     Arena A;
     A.T = Tables{P.strs.view(), P.ns.view(), ex.view(), P.row_ns, P.row_obj, P.row_rel, P.n_rows, d_ons, d_oobj, d_orel,
                  ov_base, n_ov, extra_base};
-    A.nodes = W.nodes.get<keto_tree_node>(n_nodes);
-    A.toff = W.toff.get<uint64_t>(n_trees + 1ull);
-    HIP_OK(hipMemcpy(A.nodes, nodes, n_nodes * sizeof(keto_tree_node), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(A.toff, tree_off, (n_trees + 1ull) * 8, hipMemcpyHostToDevice));
+    if (res) {
+        A.nodes = res->d_nodes;
+        A.toff = res->d_toff;
+        return A;
+    }
+    keto_tree_node* d_nodes = W.nodes.get<keto_tree_node>(n_nodes);
+    uint64_t* d_toff = W.toff.get<uint64_t>(n_trees + 1ull);
+    HIP_OK(hipMemcpy(d_nodes, nodes, n_nodes * sizeof(keto_tree_node), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_toff, tree_off, (n_trees + 1ull) * 8, hipMemcpyHostToDevice));
+    A.nodes = d_nodes;
+    A.toff = d_toff;
     return A;
 }
+
+// Where an encoder's bytes go once their total is known: the caller's buf when it can take them
+// (cap >= total), or -- `take` -- a block of that size from the pinned pool (pinned_take), handed to
+// the caller through *take before anything is written to it, so that a call that fails later leaves
+// the block with its owner.  NULL: nothing is written (a sizing call, or no bytes).
+struct Sink {
+    uint8_t* buf;
+    uint64_t cap;
+    uint8_t** take;
+    uint8_t* at(uint64_t total) const {
+        if (total == 0) return nullptr;
+        if (take) return *take = static_cast<uint8_t*>(pinned_take(total));
+        return buf && cap >= total ? buf : nullptr;
+    }
+};
 }  // namespace
 
-uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
-                           uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
-                           const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap, uint64_t* offsets) {
+static uint64_t encode_proto(Snapshot& S, const keto_tree_node* nodes, const ResidentArena* res, uint64_t n_nodes,
+                           const uint64_t* tree_off, uint32_t n_trees, uint32_t ov_base,
+                           const std::vector<RowKey>& ov_keys, uint32_t extra_base,
+                           const std::vector<std::string>& extra, const Sink& sink, uint64_t* offsets) {
     const DevView dv = device_view(S);
     HIP_OK(hipSetDevice(dv.device));
     std::lock_guard<std::mutex> lk(S.mu);
@@ -780,11 +805,11 @@ uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_
     ProtoState& P = proto_state(S, dv.device);
     const hipStream_t st = 0;
     ProtoWork& W = P.work;
-    const Arena A = upload_arena(S, P, nodes, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra);
+    const Arena A = upload_arena(S, P, nodes, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra, res);
     const Tables& T = A.T;
-    keto_tree_node* const d_nodes = A.nodes;
-    uint64_t* const d_toff = A.toff;
-    lap("upload");
+    const keto_tree_node* const d_nodes = A.nodes;
+    const uint64_t* const d_toff = A.toff;
+    lap(res ? "tables" : "upload");
     uint64_t* d_slen = W.slen.get<uint64_t>(n_nodes);
     uint64_t* d_size = W.size.get<uint64_t>(n_nodes);
     uint64_t* d_st = W.st.get<uint64_t>(2 * n_nodes);
@@ -834,7 +859,8 @@ uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_
     for (uint32_t t = 0; t <= n_trees; ++t)
         if (tree_off[t] >= n_nodes) offsets[t] = total;
     lap("scan");
-    if (!buf || cap < total || total == 0) return total;
+    uint8_t* const buf = sink.at(total);
+    if (!buf) return total;
     uint8_t* d_out = W.out.get<uint8_t>(total);
     hipLaunchKernelGGL(proto_write, g(n_nodes), dim3(256), 0, st, d_nodes, n_nodes, T, d_slen, d_size, d_root, d_pos,
                        d_out);
@@ -845,12 +871,26 @@ uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_
     return total;
 }
 
+uint64_t device_tree_proto(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
+                           uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
+                           const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap, uint64_t* offsets) {
+    return encode_proto(S, nodes, nullptr, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra,
+                      Sink{buf, cap, nullptr}, offsets);
+}
+
+uint64_t device_tree_proto_resident(Snapshot& S, const ResidentArena& res, const uint64_t* tree_off, uint32_t n_trees,
+                                    uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
+                                    const std::vector<std::string>& extra, uint8_t** bytes_out, uint64_t* offsets) {
+    return encode_proto(S, nullptr, &res, res.n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra,
+                      Sink{nullptr, 0, bytes_out}, offsets);
+}
+
 // Tree.MarshalJSON text of the same trees (the kernels above "json_"): nil[t] != 0 marks a nil tree
 // ("null"); a tree without nodes that is not nil (an error root) is empty.
-uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
-                          const uint8_t* nil, uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
-                          uint32_t extra_base, const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap,
-                          uint64_t* offsets) {
+static uint64_t encode_json(Snapshot& S, const keto_tree_node* nodes, const ResidentArena* res, uint64_t n_nodes,
+                          const uint64_t* tree_off, const uint8_t* nil, uint32_t n_trees, uint32_t ov_base,
+                          const std::vector<RowKey>& ov_keys, uint32_t extra_base, const std::vector<std::string>& extra,
+                          const Sink& sink, uint64_t* offsets) {
     const DevView dv = device_view(S);
     HIP_OK(hipSetDevice(dv.device));
     std::lock_guard<std::mutex> lk(S.mu);
@@ -867,7 +907,7 @@ uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_n
     ProtoState& P = proto_state(S, dv.device);
     const hipStream_t st = 0;
     ProtoWork& W = P.work;
-    const Arena A = upload_arena(S, P, nodes, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra);
+    const Arena A = upload_arena(S, P, nodes, n_nodes, tree_off, n_trees, ov_base, ov_keys, extra_base, extra, res);
     // run[t]: the "null" bytes of the node-less trees right before tree t, back to the last tree
     // with nodes (several such trees in a row share one node index: they need a term per tree)
     std::vector<uint64_t> run(n_trees + 1ull);
@@ -876,7 +916,7 @@ uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_n
     uint8_t* d_nil = W.jnil.get<uint8_t>(n_trees);
     HIP_OK(hipMemcpy(d_run, run.data(), (n_trees + 1ull) * 8, hipMemcpyHostToDevice));
     if (n_trees) HIP_OK(hipMemcpy(d_nil, nil, n_trees, hipMemcpyHostToDevice));
-    lap("upload");
+    lap(res ? "tables" : "upload");
     uint64_t* d_own = W.jown.get<uint64_t>(n_nodes);
     uint64_t* d_clen = W.jclen.get<uint64_t>(n_nodes);
     uint64_t* d_cat = W.jcat.get<uint64_t>(n_nodes + 1);
@@ -918,7 +958,8 @@ uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_n
     HIP_OK(hipMemcpy(offsets, d_to, (n_trees + 1ull) * 8, hipMemcpyDeviceToHost));
     const uint64_t total = offsets[n_trees];
     lap("scan");
-    if (!buf || cap < total || total == 0) return total;
+    uint8_t* const buf = sink.at(total);
+    if (!buf) return total;
     uint8_t* d_out = W.out.get<uint8_t>(total);
     if (n_nodes)
         hipLaunchKernelGGL(json_write, g(n_nodes), dim3(256), 0, st, A.nodes, n_nodes, A.T, d_cat, d_pre, d_cend, d_coff,
@@ -930,6 +971,22 @@ uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_n
     d2h_staged(P, buf, d_out, total, st);
     lap("d2h");
     return total;
+}
+
+uint64_t device_tree_json(Snapshot& S, const keto_tree_node* nodes, uint64_t n_nodes, const uint64_t* tree_off,
+                          const uint8_t* nil, uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
+                          uint32_t extra_base, const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap,
+                          uint64_t* offsets) {
+    return encode_json(S, nodes, nullptr, n_nodes, tree_off, nil, n_trees, ov_base, ov_keys, extra_base, extra,
+                     Sink{buf, cap, nullptr}, offsets);
+}
+
+uint64_t device_tree_json_resident(Snapshot& S, const ResidentArena& res, const uint64_t* tree_off, const uint8_t* nil,
+                                   uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
+                                   uint32_t extra_base, const std::vector<std::string>& extra, uint8_t** bytes_out,
+                                   uint64_t* offsets) {
+    return encode_json(S, nullptr, &res, res.n_nodes, tree_off, nil, n_trees, ov_base, ov_keys, extra_base, extra,
+                     Sink{nullptr, 0, bytes_out}, offsets);
 }
 
 }  // namespace keto

@@ -622,6 +622,26 @@ uint64_t device_tree_json(Snapshot& s, const keto_tree_node* nodes, uint64_t n_n
                           const uint8_t* nil, uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
                           uint32_t extra_base, const std::vector<std::string>& extra, uint8_t* buf, uint64_t cap,
                           uint64_t* offsets);
+// A node arena device_expand left on the device (ExpandOnDevice below): tree t = d_nodes[d_toff[t],
+// d_toff[t + 1]), d_toff holding n_trees + 1 entries.
+struct ResidentArena {
+    const keto_tree_node* d_nodes;
+    uint64_t n_nodes;
+    const uint64_t* d_toff;
+};
+// The two encoders over such an arena, without the node upload (keto_expand_encode_batch): tree_off =
+// the host's copy of d_toff; the sizes are computed once and the bytes land in a block taken from the
+// pinned pool (pinned_take) of exactly the total returned, handed out through *bytes_out (left as it
+// is when the total is 0) -- the caller gives it back with pinned_give, also when the call throws.
+// The caller orders the arena's writes before the call (the encoders run on stream 0) and keeps the
+// arena from being overwritten during it.
+uint64_t device_tree_proto_resident(Snapshot& s, const ResidentArena& res, const uint64_t* tree_off, uint32_t n_trees,
+                                    uint32_t ov_base, const std::vector<RowKey>& ov_keys, uint32_t extra_base,
+                                    const std::vector<std::string>& extra, uint8_t** bytes_out, uint64_t* offsets);
+uint64_t device_tree_json_resident(Snapshot& s, const ResidentArena& res, const uint64_t* tree_off, const uint8_t* nil,
+                                   uint32_t n_trees, uint32_t ov_base, const std::vector<RowKey>& ov_keys,
+                                   uint32_t extra_base, const std::vector<std::string>& extra, uint8_t** bytes_out,
+                                   uint64_t* offsets);
 void device_copy(void* dst, const void* src, uint64_t bytes, void* stream);   // D2D, synchronous
 void device_memory(int device, uint64_t& free_bytes, uint64_t& total_bytes);
 // packed string requests resolved and checked on the device (resolve_dev.hip); the indexes of the
@@ -702,10 +722,20 @@ struct ExpandResult {
 // (their root / vid entries are ignored).  root_rows: each subject-set root's row id (any other
 // entry ignored), which an arena whose roots lie past 2^31 units needs: such a root's handle does
 // not fit a tree node, so its node takes the row from here
+// keep != NULL: the form that stops before the node D2H (keto_expand_encode_batch).  out gets the
+// statuses and offsets, out.nodes stays empty; the finished arena (row ids in its set nodes, the
+// root and overlay fix-ups done by kernels) stays in the snapshot's device buffers, described by
+// keep->arena, every write to it complete when the call returns.  keep->hold owns the device state's
+// mutex from then on: no other expand on the snapshot overwrites the arena until the caller drops
+// it.  Not for a migrating part (KETO_E_INVALID): its pulled rows are translated on the host.
+struct ExpandOnDevice {
+    ResidentArena arena{nullptr, 0, nullptr};
+    std::unique_lock<std::mutex> hold;
+};
 void device_expand(Snapshot& s, const std::vector<uint32_t>& root, const std::vector<uint32_t>& root_flags,
                    const std::vector<uint32_t>& root_vid, const std::vector<int32_t>& depth, int32_t gmd,
                    const Overlay* ov, ExpandResult& out,
                    const std::vector<std::pair<uint32_t, uint32_t>>* remote_roots = nullptr,
-                   const std::vector<uint32_t>* root_rows = nullptr);
+                   const std::vector<uint32_t>* root_rows = nullptr, ExpandOnDevice* keep = nullptr);
 
 }  // namespace keto

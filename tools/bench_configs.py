@@ -328,6 +328,59 @@ def config5(a, g=None):
         del hb
     finally:
         lib.keto_tree_arena_free(arena)
+    # roots in, bytes out in one call (keto_expand_encode_batch_ids: the arena stays on the device)
+    # against what a caller pays today for the same bytes: keto_expand_batch_ids + the sizing and
+    # filling keto_tree_*_all_device pair into a pinned keto_host_alloc buffer, timed as one interval.
+    # Per encoding: one untimed call of each form (first-use allocations), then 3 timed repetitions of
+    # each, the best reported; bytes and offsets of every fused call compared with the host encoder's.
+    # `faster`: the fused best beats the two-step best by more than the two-step repetitions' spread
+    fused = {}
+    for enc, code, fn, want_bytes, want_offs in (("proto", 0, lib.keto_tree_proto_all_device, blob, poffs),
+                                                 ("json", 1, lib.keto_tree_json_all_device, host_text, joffs)):
+        hb = HostBuffer(max(1, len(want_bytes)), np.uint8)
+        offs2 = np.zeros(n + 1, dtype=np.uint64)
+
+        def two_step():
+            arena = C.c_void_p()
+            t0 = time.perf_counter()
+            rc = lib.keto_expand_batch_ids(snap.h, roots.ctypes.data_as(C.c_void_p), depths.ctypes.data_as(C.c_void_p),
+                                           C.c_uint32(n), C.c_int32(5), C.byref(arena))
+            total = fn(snap.h, arena, None, C.c_uint64(0), offs2.ctypes.data_as(C.c_void_p))
+            got = fn(snap.h, arena, hb.array.ctypes.data_as(C.c_void_p), C.c_uint64(max(0, total)),
+                     offs2.ctypes.data_as(C.c_void_p))
+            dt = time.perf_counter() - t0
+            lib.keto_tree_arena_free(arena)
+            assert rc == 0 and got == total == len(want_bytes), (rc, total, got, lib.keto_last_error())
+            return dt
+
+        def one_call():
+            e = C.c_void_p()
+            t0 = time.perf_counter()
+            rc = lib.keto_expand_encode_batch_ids(snap.h, roots.ctypes.data_as(C.c_void_p),
+                                                  depths.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_int32(5),
+                                                  C.c_uint32(code), C.byref(e))
+            dt = time.perf_counter() - t0
+            assert rc == 0, lib.keto_last_error()
+            try:
+                total = C.c_uint64()
+                p = lib.keto_encoded_bytes(e, C.byref(total))
+                offs_f = np.frombuffer(C.string_at(lib.keto_encoded_offsets(e), 8 * (n + 1)), dtype=np.uint64)
+                assert C.string_at(p, total.value) == want_bytes and bool((offs_f == want_offs).all()), enc
+            finally:
+                lib.keto_encoded_free(e)
+            return dt
+
+        two_step()
+        one_call()
+        sums = [two_step() for _ in range(3)]
+        reps = [one_call() for _ in range(3)]
+        assert hb.array[:len(want_bytes)].tobytes() == want_bytes
+        del hb
+        fused[enc] = {"wall_ms": round(min(reps) * 1e3, 3), "reps_ms": [round(x * 1e3, 3) for x in reps],
+                      "two_step_ms": round(min(sums) * 1e3, 3), "two_step_reps_ms": [round(x * 1e3, 3) for x in sums],
+                      "two_step_spread_ms": round((max(sums) - min(sums)) * 1e3, 3),
+                      "ratio": round(min(sums) / min(reps), 2),
+                      "faster": bool(min(reps) < min(sums) - (max(sums) - min(sums))), "bytes_equal_host": True}
     # node-by-node comparison of a sample of trees with the oracle (pre-order, child order included)
     from tests.test_gpu_synth import _oracle_expand_nodes
     k = a.expand_sample
@@ -398,6 +451,11 @@ def config5(a, g=None):
                             "what": "keto_tree_json_all_device: the same text encoded on the GPU (node upload, sizes, "
                                     "closes, scan, write, D2H), sizing + filling call, into fresh pageable numpy memory "
                                     "(pinned bounce chunks) and into a pinned caller buffer (keto_host_alloc)"},
+            "expand_encoded": dict(fused, what="keto_expand_encode_batch_ids: H2D roots, the expand passes, fix-ups and "
+                                               "one run of the size kernels on the device-resident arena, write, one DMA "
+                                               "into a pinned-pool block; two_step = keto_expand_batch_ids + the sizing and "
+                                               "filling keto_tree_*_all_device pair into a keto_host_alloc buffer, one "
+                                               "interval; both after one untimed call, best of 3"),
             "parity": {"sample_trees": k, "sample_nodes": n_nodes, "mismatched_trees": bad}}
 
 
