@@ -621,6 +621,77 @@ const uint8_t* keto_encoded_bytes(const keto_encoded* e, uint64_t* total_out);
 const uint64_t* keto_encoded_offsets(const keto_encoded* e);           /* n + 1; tree i = bytes[off[i], off[i+1]) */
 const uint8_t* keto_encoded_status(const keto_encoded* e);             /* n x KETO_EXPAND_* */
 
+/* ---- Lists: ListRelationTuples from the snapshot (repo:keto_amd/csrc/list.hip) ----
+ * keto_list_batch replaces, for a batch of queries, relationtuple.Manager.GetRelationTuples as a list:
+ * ReadService.ListRelationTuples and GET /relation-tuples (internal/relationtuple/read_server.go:21-48,
+ * 114-154), which end in sql.(*Persister).GetRelationTuples (internal/persistence/sql/relationtuples.go:
+ * 238-277) with whereQuery (:178-198) and, for a subject, whereSubject (:151-176).  Per query the
+ * result is the matching tuples in the reference's ORDER BY (:250; SQLite: subject sets before subject
+ * ids), duplicates kept, rows [(page-1) * size, page * size) of them with page = max(page, 1), the
+ * next page token and the count of all matches (pop's COUNT(*) behind the token):
+ * next_page = page + 1 unless page >= ceil(total / size), then 0 -- so 0 when nothing matches and 0
+ * past the end (:262-265).  Materialized wildcard rows (row keys with an empty field) and batch-local
+ * rows are views of other rows' tuples, not tuples: they are never listed.  A stored subject set with
+ * an empty field is a tuple; its `subject` names its materialized row, which keto_subject_fields
+ * prints with the empty field.
+ *
+ * A tuple is {row id (snapshot row order), subject reference as in keto_tree_node.subject}: the caller
+ * gets namespace, object and relation from keto_subject_fields(s, NULL, {row | 0x80000000}, ...) and
+ * the subject from the same call.  Row ids and string ids are only ever appended by
+ * keto_snapshot_apply (repo:keto_amd/csrc/delta.cpp, the commit: new strings and row keys are
+ * pushed behind the existing ones, none moves), so a result stays decodable after later writes.  The
+ * tuple block lives in the library's pinned pool, like a keto_encoded result's bytes, sized exactly
+ * after the count pass (min(size, total - first) per query): a huge page_size allocates nothing.
+ *
+ * Poisoned tuples (a namespace id, or a subject set's namespace id, the config lacks: toInternal
+ * fails, :43-80) have lost their subject in the snapshot.  Without a subject filter the answer is
+ * still exact: KETO_LIST_NOT_FOUND iff such a tuple falls inside the page.  With a subject filter, a
+ * poisoned tuple anywhere among the tuples matching the query's namespace, object and relation could
+ * be a match the snapshot cannot see: the query is KETO_LIST_UNDECIDED and the caller asks the
+ * reference.
+ *
+ * The first list call on a snapshot version builds the list index on host threads and uploads it
+ * (8 B per tuple plus 8 B per row of device memory, counted in keto_snapshot_stats.device_bytes); a
+ * write invalidates it and the next list call rebuilds all of it (no incremental patching).
+ * Errors: a host-only snapshot is KETO_E_HIP, any part of a partitioned upload (n_parts > 1)
+ * KETO_E_INVALID; n = 0 gives count 0 and offsets {0}.  Calls take the snapshot's lock shared, as
+ * keto_expand_batch does, and run one at a time per snapshot. */
+#define KETO_LIST_OK 0          /* tuples, next_page and total equal the reference's */
+#define KETO_LIST_NOT_FOUND 1   /* herodot.ErrNotFound: unknown query namespace or subject-set namespace
+                                   (GetNamespaceByName, relationtuples.go:161,180), or a tuple OF THE PAGE
+                                   fails toInternal (:43-80, :268-274); no tuples */
+#define KETO_LIST_UNDECIDED 2   /* the snapshot cannot tell (above): ask the reference; no tuples */
+
+typedef struct {
+    keto_str namespace_, object, relation;  /* empty = not filtered (whereQuery :179-191) */
+    uint8_t has_subject;                    /* 0: RelationQuery.Subject() == nil */
+    keto_subject subject;                   /* typed, exact equality on every field (whereSubject :151-176) */
+    uint32_t page_size;                     /* 0 -> the snapshot's page_size (defaultPageSize, persister.go:46,111-113) */
+    uint32_t page;                          /* the decimal page token; 0 = "" = page 1 (persister.go:117-130) */
+} keto_list_req;
+typedef struct { uint32_t row; uint32_t subject; } keto_list_tuple;
+typedef struct keto_listed keto_listed;
+int keto_list_batch(keto_snapshot* s, const keto_list_req* reqs, uint32_t n, keto_listed** out);
+void keto_listed_free(keto_listed*);                          /* NULL is fine */
+uint32_t keto_listed_count(const keto_listed*);               /* n */
+const keto_list_tuple* keto_listed_tuples(const keto_listed*, uint64_t* total_out);
+const uint64_t* keto_listed_offsets(const keto_listed*);      /* n+1; query i = tuples[off[i], off[i+1]) */
+const uint8_t*  keto_listed_status(const keto_listed*);       /* n x KETO_LIST_* */
+const uint64_t* keto_listed_next_page(const keto_listed*);    /* 0 = "" (last page), else the token's number */
+const uint64_t* keto_listed_totals(const keto_listed*);       /* matches of the whole query (pop's COUNT) */
+/* of the call that made the result: index_ms = the list index (re)built first (0 when it was current),
+ * scan_ms = the count, scan and emit passes on the device (HIP events) */
+int keto_listed_timing(const keto_listed*, float* index_ms, float* scan_ms);
+/* host only; works on device = -1 snapshots: what the scan will be asked to do.  [lo, hi) = the entries
+ * of the list index (all tuples in ORDER BY order) the query is narrowed to by binary search over the
+ * rows in key order (namespace: its run; namespace + object: narrower; all three: one row; lo == hi
+ * when a filter names an unknown string or subject); ns / obj / rel / subject = what the scan still
+ * compares per entry (obj / rel: string ids, subject: the entry word; 0xFFFFFFFF = not compared);
+ * ns = the namespace id the range is the run of (INT64_MIN: no namespace filter; the scan never
+ * compares it); status = KETO_LIST_OK or KETO_LIST_NOT_FOUND (unknown namespace). */
+typedef struct { uint64_t lo, hi; int64_t ns; uint32_t obj, rel, subject; uint8_t status; } keto_list_plan_t;
+int keto_list_plan(const keto_snapshot* s, const keto_list_req* reqs, uint32_t n, keto_list_plan_t* out);
+
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,
  * internal/relationtuple/definitions.go:40-42,102-117) straight from the node arena without a text

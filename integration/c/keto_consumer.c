@@ -511,6 +511,55 @@ static void subject_of(line_t* l, int* k, keto_subject* s) {
     }
 }
 
+/* One list round trip (keto_list_batch, ListRelationTuples from the snapshot): the first page of the
+ * unfiltered query, i.e. of every tuple of the table.  A host-only snapshot must fail with KETO_E_HIP
+ * and a part of a partitioned upload with KETO_E_INVALID.  On a device the page holds min(page size,
+ * total) tuples whose rows and subjects decode through keto_subject_fields, total is the table's tuple
+ * count and the token says whether a second page exists -- unless a tuple of the page is poisoned
+ * (KETO_LIST_NOT_FOUND, no tuples).  Returns 0, or the process's exit code. */
+static int list_round_trip(keto_snapshot* s, int device, int n_parts, uint32_t page_size) {
+    keto_list_req q;
+    memset(&q, 0, sizeof q);
+    keto_listed* l = NULL;
+    const int rc = keto_list_batch(s, &q, 1, &l);
+    if (n_parts > 1 || device < 0) {
+        const int want = n_parts > 1 ? KETO_E_INVALID : KETO_E_HIP;
+        printf("list\t%d\n", rc);
+        return rc == want && keto_last_error()[0] && !l ? 0 : 16;
+    }
+    if (rc != KETO_OK) fail("keto_list_batch", rc);
+    keto_snapshot_stats st;
+    if (keto_snapshot_get_stats(s, &st) != KETO_OK) return 16;
+    uint64_t n = 0;
+    const keto_list_tuple* t = keto_listed_tuples(l, &n);
+    const uint64_t* off = keto_listed_offsets(l);
+    const uint8_t status = keto_listed_status(l)[0];
+    const uint64_t total = keto_listed_totals(l)[0], next = keto_listed_next_page(l)[0];
+    const uint64_t ps = page_size ? page_size : 100;
+    int bad = keto_listed_count(l) != 1 || off[0] != 0 || off[1] != n;
+    if (status == KETO_LIST_OK) {
+        bad |= total != st.n_tuples || n != (total < ps ? total : ps) || next != (total > ps ? 2u : 0u);
+        if (!bad && n) {
+            uint32_t* refs = (uint32_t*)malloc(2 * n * sizeof(uint32_t));
+            uint32_t* lens = (uint32_t*)malloc(6 * n * sizeof(uint32_t));
+            if (!refs || !lens) return 3;
+            for (uint64_t k = 0; k < n; ++k) {
+                refs[2 * k] = t[k].row | 0x80000000u;      /* namespace, object, relation of the tuple */
+                refs[2 * k + 1] = t[k].subject;
+            }
+            bad |= keto_subject_fields(s, NULL, refs, 2 * n, NULL, 0, lens) < 0;
+            free(refs);
+            free(lens);
+        }
+    } else {
+        bad |= status != KETO_LIST_NOT_FOUND || n != 0;   /* no subject filter: never undecided */
+    }
+    printf("list\t%d\t%u\t%llu\t%llu\t%llu\n", rc, status, (unsigned long long)n, (unsigned long long)total,
+           (unsigned long long)next);
+    keto_listed_free(l);
+    return bad ? 16 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <input>\n", argv[0]);
@@ -824,6 +873,8 @@ int main(int argc, char** argv) {
     /* an error path: a NULL argument must fail with a message, not crash */
     rc = keto_check_batch(reps[0], NULL, 1, 5, NULL, NULL);
     if (rc != KETO_E_INVALID || !keto_last_error()[0]) return 8;
+    rc = list_round_trip(reps[0], parted ? part.devices[0] : devices[0], parted ? part.n : 1, page_size);
+    if (rc) return rc;
     if (parted)
         partition_release(&part);
     else

@@ -14,6 +14,7 @@ import (
 	"github.com/ory/keto/internal/gpu"
 	"github.com/ory/keto/internal/persistence"
 	"github.com/ory/keto/internal/relationtuple"
+	"github.com/ory/keto/internal/x"
 )
 
 // The registry side of the GPU path.  After Init (internal/driver/registry_default.go:241-262) the
@@ -54,6 +55,13 @@ func GPUDevicesFromEnv() []int {
 		out = append(out, d)
 	}
 	return out
+}
+
+// gpuListSource is the persister's list dispatch (internal/persistence/sql/snapshot_gpu.go).
+type gpuListSource interface {
+	GetRelationTuplesFromSnapshot(ctx context.Context,
+		list func(qs []gpu.ListQuery) (res []gpu.ListResult, ok bool, err error), query *relationtuple.RelationQuery,
+		options ...x.PaginationOptionSetter) ([]*relationtuple.InternalRelationTuple, string, error)
 }
 
 // gpuRowSource is the persister's full scan (internal/persistence/sql/snapshot_gpu.go).
@@ -134,6 +142,24 @@ func (r *RegistryDefault) GPUCheckBatcher() *gpu.Batcher {
 		return nil
 	}
 	return st.check
+}
+
+// ListTuples is the GPU side of the list dispatch: ListRelationTuples queries from a replica at the table's
+// version.  ok is false while the engines are stale and for a partitioned placement (a part holds only
+// some rows): SQL answers then.  The read lock is held over the call, so a rebuild cannot close the
+// replica under it.
+func (g *gpuState) ListTuples(qs []gpu.ListQuery) ([]gpu.ListResult, bool, error) {
+	g.mu.RLock()
+	defer g.mu.RUnlock()
+	if g.stale || len(g.engines) == 0 {
+		return nil, false, nil
+	}
+	s, ok := g.engines[0].(*gpu.Snapshot)
+	if !ok {
+		return nil, false, nil
+	}
+	res, err := s.ListBatch(qs)
+	return res, err == nil, err
 }
 
 // GPUExpandBatcher implements expand.GPUProvider (nil: answer on SQL).
@@ -328,6 +354,16 @@ func (g *gpuState) rebuild() {
 type gpuPersister struct {
 	persistence.Persister
 	g *gpuState
+}
+
+// GetRelationTuples serves the list calls (and the SQL engines' own reads) from the snapshot when it
+// can answer exactly (internal/persistence/sql/snapshot_gpu.go), from SQL otherwise.
+func (p *gpuPersister) GetRelationTuples(ctx context.Context, query *relationtuple.RelationQuery,
+	options ...x.PaginationOptionSetter) ([]*relationtuple.InternalRelationTuple, string, error) {
+	if sp, ok := p.Persister.(gpuListSource); ok {
+		return sp.GetRelationTuplesFromSnapshot(ctx, p.g.ListTuples, query, options...)
+	}
+	return p.Persister.GetRelationTuples(ctx, query, options...)
 }
 
 func (p *gpuPersister) WriteRelationTuples(ctx context.Context, rs ...*relationtuple.InternalRelationTuple) error {

@@ -735,3 +735,107 @@ func (s *Snapshot) subjects(a *C.keto_tree_arena, refs []uint32, m *cmem) ([]rel
 		return out, nil
 	}
 }
+
+// List statuses of ListBatch (KETO_LIST_*).
+const (
+	ListOK        = uint8(C.KETO_LIST_OK)
+	ListNotFound  = uint8(C.KETO_LIST_NOT_FOUND) // herodot.ErrNotFound in the reference: unknown namespace, or a page holding a tuple of one
+	ListUndecided = uint8(C.KETO_LIST_UNDECIDED) // the snapshot cannot tell: ask the SQL persister
+)
+
+// ListQuery is one relationtuple.RelationQuery with its pagination (keto_list_req): empty Namespace /
+// Object / Relation do not filter, a nil Subject does not either; PageSize 0 is the snapshot's page
+// size and Page 0 the empty token (page 1).
+type ListQuery struct {
+	Namespace, Object, Relation string
+	Subject                     relationtuple.Subject
+	PageSize, Page              uint32
+}
+
+// ListResult is one query's page: the tuples in the reference's ORDER BY, the next page token's
+// number (0: the empty token, last page) and the count of all matches.  Tuples are set only when
+// Status is ListOK.
+type ListResult struct {
+	Status   uint8
+	Tuples   []*relationtuple.InternalRelationTuple
+	NextPage uint64
+	Total    uint64
+}
+
+// ListBatch = sql.(*Persister).GetRelationTuples as a list
+// (internal/persistence/sql/relationtuples.go:238-277) for many queries, from the snapshot
+// (keto_list_batch).  The tuples come back as {row id, subject reference} pairs; their strings are
+// read with keto_subject_fields, one call for every distinct reference of the batch.  Not for a
+// Partition: a part holds only some rows (KETO_E_INVALID).
+func (s *Snapshot) ListBatch(qs []ListQuery) ([]ListResult, error) {
+	n := len(qs)
+	if n == 0 {
+		return nil, nil
+	}
+	var m cmem
+	defer m.free()
+	total := 0
+	for i := range qs {
+		total += len(qs[i].Namespace) + len(qs[i].Object) + len(qs[i].Relation) + subjectLen(qs[i].Subject)
+	}
+	m.strings(total)
+	cr := (*C.keto_list_req)(m.alloc(n * int(C.sizeof_keto_list_req)))
+	cs := unsafe.Slice(cr, n)
+	for i := range qs {
+		q := &qs[i]
+		cs[i] = C.keto_list_req{namespace_: m.s(q.Namespace), object: m.s(q.Object), relation: m.s(q.Relation),
+			page_size: C.uint32_t(q.PageSize), page: C.uint32_t(q.Page)}
+		if q.Subject != nil {
+			cs[i].has_subject = 1
+			cs[i].subject = m.subject(q.Subject)
+		}
+	}
+	var l *C.keto_listed
+	if rc := C.keto_list_batch(s.h, cr, C.uint32_t(n), &l); rc != C.KETO_OK {
+		return nil, lastErr(rc)
+	}
+	defer C.keto_listed_free(l)
+	var count C.uint64_t
+	tp := C.keto_listed_tuples(l, &count)
+	off := unsafe.Slice(C.keto_listed_offsets(l), n+1)
+	status := unsafe.Slice(C.keto_listed_status(l), n)
+	next := unsafe.Slice(C.keto_listed_next_page(l), n)
+	totals := unsafe.Slice(C.keto_listed_totals(l), n)
+	var tuples []C.keto_list_tuple
+	if tp != nil && count > 0 {
+		tuples = unsafe.Slice(tp, int(count)) // the result's memory: read before keto_listed_free
+	}
+	// every distinct reference once: a tuple's row (as the subject set of its namespace, object and
+	// relation) and its subject
+	refIdx := make(map[uint32]int)
+	var refs []uint32
+	add := func(ref uint32) {
+		if _, ok := refIdx[ref]; !ok {
+			refIdx[ref] = len(refs)
+			refs = append(refs, ref)
+		}
+	}
+	for _, t := range tuples {
+		add(uint32(t.row) | 0x80000000)
+		add(uint32(t.subject))
+	}
+	subjects, err := s.subjects(nil, refs, &m)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]ListResult, n)
+	for i := 0; i < n; i++ {
+		out[i] = ListResult{Status: uint8(status[i]), NextPage: uint64(next[i]), Total: uint64(totals[i])}
+		if out[i].Status != ListOK {
+			continue
+		}
+		page := tuples[int(off[i]):int(off[i+1])]
+		out[i].Tuples = make([]*relationtuple.InternalRelationTuple, len(page))
+		for k, t := range page {
+			row := subjects[refIdx[uint32(t.row)|0x80000000]].(*relationtuple.SubjectSet)
+			out[i].Tuples[k] = &relationtuple.InternalRelationTuple{Namespace: row.Namespace, Object: row.Object,
+				Relation: row.Relation, Subject: subjects[refIdx[uint32(t.subject)]]}
+		}
+	}
+	return out, nil
+}

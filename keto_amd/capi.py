@@ -44,7 +44,10 @@ EXPORTS = [
     "keto_snapshot_save", "keto_snapshot_load", "keto_expand_batch_routed",
     "keto_expand_encode_batch", "keto_expand_encode_batch_ids", "keto_encoded_free", "keto_encoded_count",
     "keto_encoded_bytes", "keto_encoded_offsets", "keto_encoded_status",
+    "keto_list_batch", "keto_listed_free", "keto_listed_count", "keto_listed_tuples", "keto_listed_offsets",
+    "keto_listed_status", "keto_listed_next_page", "keto_listed_totals", "keto_listed_timing", "keto_list_plan",
 ]
+LIST_OK, LIST_NOT_FOUND, LIST_UNDECIDED = 0, 1, 2
 ENC_PROTO, ENC_JSON = 0, 1
 ENCODINGS = {"proto": ENC_PROTO, "json": ENC_JSON}
 PART_SHARED, PART_MIGRATE = 0, 1
@@ -123,6 +126,19 @@ def pairs_of(q: np.ndarray) -> np.ndarray:
 
 class KExpandReq(C.Structure):
     _fields_ = [("subject", KSubject), ("max_depth", C.c_int32)]
+
+
+class KListReq(C.Structure):
+    _fields_ = [("namespace_", KStr), ("object", KStr), ("relation", KStr), ("has_subject", C.c_uint8),
+                ("subject", KSubject), ("page_size", C.c_uint32), ("page", C.c_uint32)]
+
+
+class KListPlan(C.Structure):
+    _fields_ = [("lo", C.c_uint64), ("hi", C.c_uint64), ("ns", C.c_int64), ("obj", C.c_uint32), ("rel", C.c_uint32),
+                ("subject", C.c_uint32), ("status", C.c_uint8)]
+
+
+LIST_TUPLE_DTYPE = np.dtype([("row", "<u4"), ("subject", "<u4")])
 
 
 class KTreeNode(C.Structure):
@@ -213,6 +229,17 @@ def load():
         lib.keto_encoded_offsets.argtypes = [C.c_void_p]
         lib.keto_encoded_status.restype = C.c_void_p
         lib.keto_encoded_status.argtypes = [C.c_void_p]
+    if hasattr(lib, "keto_list_batch"):
+        lib.keto_listed_free.restype = None
+        lib.keto_listed_free.argtypes = [C.c_void_p]
+        lib.keto_listed_count.restype = C.c_uint32
+        lib.keto_listed_count.argtypes = [C.c_void_p]
+        lib.keto_listed_tuples.restype = C.c_void_p
+        lib.keto_listed_tuples.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        for f in (lib.keto_listed_offsets, lib.keto_listed_status, lib.keto_listed_next_page, lib.keto_listed_totals):
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p]
+        lib.keto_listed_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.keto_route_work_bytes.argtypes = [C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
@@ -782,6 +809,75 @@ class Snapshot:
         trees, "" for errors)."""
         offs, raw, _ = self._json_all_raw(a, n, device=device)
         return [raw[int(offs[i]):int(offs[i + 1])].decode() for i in range(n)]
+
+    # ------------------------------------------------------------------ list
+    @staticmethod
+    def _list_reqs(keep, queries):
+        """queries: (namespace, object, relation, subject or None, page_size, page) with subject as in
+        check_batch, page_size 0 = the snapshot's and page 0 = "" = the first -> a KListReq array."""
+        arr = (KListReq * max(1, len(queries)))()
+        for k, (ns, obj, rel, sub, size, page) in enumerate(queries):
+            arr[k].namespace_ = keep.s(ns)
+            arr[k].object = keep.s(obj)
+            arr[k].relation = keep.s(rel)
+            arr[k].has_subject = 0 if sub is None else 1
+            if sub is not None:
+                arr[k].subject = subject_struct(keep, sub)
+            arr[k].page_size = size
+            arr[k].page = page
+        return arr
+
+    def list_plan(self, queries):
+        """keto_list_plan (host only, any snapshot): per query a dict of the entry range [lo, hi) of the
+        list index, the predicates left to the scan (None: not compared) and the status."""
+        keep = _Keep()
+        n = len(queries)
+        out = (KListPlan * max(1, n))()
+        _check(self.lib.keto_list_plan(self.h, self._list_reqs(keep, queries), C.c_uint32(n), out))
+        opt = lambda v: None if v == 0xFFFFFFFF else int(v)
+        return [{"lo": int(p.lo), "hi": int(p.hi), "ns": None if p.ns == -(1 << 63) else int(p.ns), "obj": opt(p.obj),
+                 "rel": opt(p.rel), "subject": opt(p.subject), "status": int(p.status)} for p in out[:n]]
+
+    def list_batch_raw(self, queries):
+        """keto_list_batch -> (status[n], offsets[n+1], tuples (LIST_TUPLE_DTYPE), next_page[n], totals[n],
+        (index_ms, scan_ms)), copied out of the keto_listed handle, which is freed here."""
+        keep = _Keep()
+        n = len(queries)
+        h = C.c_void_p()
+        _check(self.lib.keto_list_batch(self.h, self._list_reqs(keep, queries), C.c_uint32(n), C.byref(h)))
+        try:
+            assert self.lib.keto_listed_count(h) == n
+            total = C.c_uint64()
+            p = self.lib.keto_listed_tuples(h, C.byref(total))
+            get = lambda f, nbytes, dt: np.frombuffer(C.string_at(f(h), nbytes), dtype=dt).copy()
+            status = get(self.lib.keto_listed_status, n, np.uint8)
+            offs = get(self.lib.keto_listed_offsets, 8 * (n + 1), np.uint64)
+            nxt = get(self.lib.keto_listed_next_page, 8 * n, np.uint64)
+            tot = get(self.lib.keto_listed_totals, 8 * n, np.uint64)
+            tup = (np.frombuffer(C.string_at(p, 8 * total.value), dtype=LIST_TUPLE_DTYPE).copy() if total.value
+                   else np.zeros(0, dtype=LIST_TUPLE_DTYPE))
+            ims, sms = C.c_float(), C.c_float()
+            _check(self.lib.keto_listed_timing(h, C.byref(ims), C.byref(sms)))
+        finally:
+            self.lib.keto_listed_free(h)
+        return status, offs, tup, nxt, tot, (ims.value, sms.value)
+
+    def decode_list_tuples(self, tup):
+        """LIST_TUPLE_DTYPE entries -> [(namespace, object, relation, subject)] with subject ("id", id) or
+        ("set", namespace, object, relation), through keto_subject_fields alone."""
+        if len(tup) == 0:
+            return []
+        rows = self.subject_fields(tup["row"] | np.uint32(0x80000000))
+        subs = self.subject_fields(tup["subject"])
+        return [(r[1], r[2], r[3], s) for r, s in zip(rows, subs)]
+
+    def list_batch(self, queries):
+        """ListRelationTuples for a batch: queries as in list_plan -> per query (status, [(namespace, object,
+        relation, subject)], next page token ("" = last page), total matches)."""
+        status, offs, tup, nxt, tot, _ = self.list_batch_raw(queries)
+        dec = self.decode_list_tuples(tup)
+        return [(int(status[i]), dec[int(offs[i]):int(offs[i + 1])], str(int(nxt[i])) if nxt[i] else "", int(tot[i]))
+                for i in range(len(queries))]
 
     def subject_fields(self, refs, arena=None):
         """keto_subject_fields: per subject reference ("id", id) or ("set", namespace, object, relation)."""

@@ -429,7 +429,7 @@ int keto_snapshot_get_stats(const keto_snapshot* h, keto_snapshot_stats* out) {
         out->n_poisoned_rows = S.n_poisoned_rows;
         out->n_strings = (uint32_t)S.strs.size();
         out->n_collision_keys = S.n_coll_keys;
-        out->device_bytes = device_bytes(S);
+        out->device_bytes = device_bytes(S) + list_device_bytes(h->list);   // the list index, once a list call built it
         return KETO_OK;
     });
 }
@@ -1296,6 +1296,59 @@ const uint8_t* keto_encoded_bytes(const keto_encoded* e, uint64_t* total_out) {
 const uint64_t* keto_encoded_offsets(const keto_encoded* e) { return e ? e->offsets.data() : nullptr; }
 
 const uint8_t* keto_encoded_status(const keto_encoded* e) { return e ? e->status.data() : nullptr; }
+
+// ---- keto_list_batch: ListRelationTuples from the snapshot (list.hip)
+struct keto_listed {
+    ListResult r;                           // r.tuples: a block of the pinned pool, or NULL
+    ~keto_listed() { pinned_give(r.tuples); }
+};
+
+int keto_list_batch(keto_snapshot* h, const keto_list_req* reqs, uint32_t n, keto_listed** out) {
+    return guarded([&] {
+        if (!h || !out || (n && !reqs)) throw Error{KETO_E_INVALID, "NULL argument"};
+        *out = nullptr;
+        std::shared_lock<RwGate> lk(h->s->rw);
+        auto l = std::make_unique<keto_listed>();
+        list_batch(*h->s, h->list, reqs, n, l->r);
+        *out = l.release();
+        return KETO_OK;
+    });
+}
+
+void keto_listed_free(keto_listed* l) { delete l; }
+
+uint32_t keto_listed_count(const keto_listed* l) { return l ? (uint32_t)l->r.status.size() : 0; }
+
+const keto_list_tuple* keto_listed_tuples(const keto_listed* l, uint64_t* total_out) {
+    if (total_out) *total_out = l ? l->r.offsets.back() : 0;
+    return l ? l->r.tuples : nullptr;
+}
+
+const uint64_t* keto_listed_offsets(const keto_listed* l) { return l ? l->r.offsets.data() : nullptr; }
+
+const uint8_t* keto_listed_status(const keto_listed* l) { return l ? l->r.status.data() : nullptr; }
+
+const uint64_t* keto_listed_next_page(const keto_listed* l) { return l ? l->r.next_page.data() : nullptr; }
+
+const uint64_t* keto_listed_totals(const keto_listed* l) { return l ? l->r.totals.data() : nullptr; }
+
+int keto_listed_timing(const keto_listed* l, float* index_ms, float* scan_ms) {
+    return guarded([&] {
+        if (!l) throw Error{KETO_E_INVALID, "NULL argument"};
+        if (index_ms) *index_ms = l->r.index_ms;
+        if (scan_ms) *scan_ms = l->r.scan_ms;
+        return KETO_OK;
+    });
+}
+
+int keto_list_plan(const keto_snapshot* h, const keto_list_req* reqs, uint32_t n, keto_list_plan_t* out) {
+    return guarded([&] {
+        if (!h || (n && (!reqs || !out))) throw Error{KETO_E_INVALID, "NULL argument"};
+        std::shared_lock<RwGate> lk(h->s->rw);
+        list_plan(*h->s, h->list, reqs, n, out);
+        return KETO_OK;
+    });
+}
 
 int64_t keto_subject_fields(const keto_snapshot* h, const keto_tree_arena* a, const uint32_t* subjects, uint64_t n,
                             char* buf, uint64_t cap, uint32_t* lens_out) {

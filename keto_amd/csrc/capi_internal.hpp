@@ -9,10 +9,14 @@
 #include <string>
 #include <vector>
 
+#include "list.hpp"
 #include "snapshot.hpp"
 
 struct keto_snapshot {
     std::unique_ptr<keto::Snapshot> s;
+    // keto_list_batch / keto_list_plan: the list index of s's current version (list.hip), freed with
+    // the handle, before s and its device state
+    mutable keto::ListCache list;
 };
 
 struct keto_tree_arena {

@@ -1,0 +1,638 @@
+// ListRelationTuples from the snapshot: keto_list_batch / keto_list_plan.
+//
+// Replaces, for a batch of queries, sql.(*Persister).GetRelationTuples as a list
+// (internal/persistence/sql/relationtuples.go:238-277, paths relative to the reference tree): whereQuery
+// (:178-198) with the optional whereSubject (:151-176), the ORDER BY (:250), pop's LIMIT / OFFSET page
+// and the COUNT(*) behind the next page token (:262-265), and toInternal over the page (:43-80,
+// :268-274).
+//
+// The list index (per snapshot version, built on the first list call after a write):
+//   T[]     8-B entries {row id, subject word} of every tuple in the global ORDER BY: the tuple rows
+//           (keys without an ANY field; materialized wildcard rows are views and stay out) in key
+//           order -- Snapshot::rows_in_key_order -- and inside a row its full ORDER BY sequence,
+//           duplicates and EDGE_POISON markers included (Snapshot::row_edges).  On the device.
+//   keys[]  per row id {object string id, relation string id}: what a scan compares when the entry
+//           range alone does not imply the filter.  On the device.
+//   ord[], first[]  the tuple rows in key order and the first entry of each: the resolver's binary
+//           searches.  On the host (no kernel reads them).
+// A query resolves to an entry range [lo, hi) -- a namespace filter is always a contiguous run of
+// ord, namespace + object a narrower one, all three one row -- and the predicates left over (object
+// or relation without the fields before it, the subject word).  The scan is a filtered, ordered
+// stream compaction of that range:
+//   list_count  one 256-thread block per (query, tile) item, each wave a quarter of the tile, 16-B
+//               loads of two entries per lane, matches counted with 64-bit ballots; writes the item's
+//               count and its four wave counts
+//   scan        hipcub exclusive sum over the item counts (64-bit); a query's total is the distance
+//               between its first item's base and the next query's
+//   list_emit   items whose rank range misses the page window exit; the others recompute their
+//               matches and store those whose rank = item base + waves before + matches before in
+//               the wave falls in the window at out[offset + rank - window start]
+// No atomic decides an order: the only atomics OR a per-query poison flag.  One host sync sits between
+// the passes (totals -> result sizes, statuses, tokens).
+//
+// Known limit: a write (keto_snapshot_apply) invalidates the whole index; the next list call
+// rebuilds and uploads all of it.  Patching it in place is not done.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "hip_check.hpp"
+#include "list.hpp"
+#include "parallel.hpp"
+#include "snapshot.hpp"
+
+namespace keto {
+
+namespace {
+
+inline std::string_view sv(const keto_str& s) { return std::string_view(s.p ? s.p : "", s.n); }
+
+constexpr uint32_t LIST_THREADS = 256;
+constexpr uint32_t LIST_WAVES = LIST_THREADS / 64;
+constexpr uint64_t LIST_GROUP_ITEMS = 1ull << 20;   // items per launch (a bigger batch runs in query groups)
+
+struct LQuery {          // what the scan is asked: entries [lo, hi), predicates (ANY: not compared)
+    uint64_t lo, hi;
+    uint32_t obj, rel, subj, pad;
+};
+struct LWindow {         // ranks [wlo, whi) of the query's matches go to out[off ...)
+    uint64_t wlo, whi, off;
+};
+struct LItem {
+    uint32_t q, tile;
+};
+
+struct LBuf {            // a grow-only device buffer
+    void* p = nullptr;
+    uint64_t cap = 0;
+    LBuf() = default;
+    LBuf(const LBuf&) = delete;
+    LBuf& operator=(const LBuf&) = delete;
+    template <class T>
+    T* get(uint64_t n) {
+        const uint64_t want = std::max<uint64_t>(16, n * sizeof(T));
+        if (want > cap) {
+            release();
+            const hipError_t e = hipMalloc(&p, want + want / 8);
+            if (e != hipSuccess) {
+                p = nullptr;
+                throw Error{KETO_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)};
+            }
+            cap = want + want / 8;
+        }
+        return (T*)p;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    ~LBuf() { release(); }
+};
+
+// does entry e pass the query's row-key predicates / is it a match
+__device__ inline void list_test(const LQuery& Q, const uint2* __restrict__ keys, uint2 e, bool& match, bool& poison) {
+    bool k = true;
+    if (Q.obj != ANY || Q.rel != ANY) {
+        const uint2 key = keys[e.x];
+        k = (Q.obj == ANY || key.x == Q.obj) && (Q.rel == ANY || key.y == Q.rel);
+    }
+    poison = k && e.y == EDGE_POISON;
+    match = k && (Q.subj == ANY || e.y == Q.subj);
+}
+
+// The two entries a lane holds of the wave's 128-entry step starting at the even entry p0: e0 = p0 +
+// 2 lane and e0 + 1, tested when they lie in the wave's range [ws, we).  T is padded to an even
+// count, so the 16-B load of a pair whose second entry is past the range stays inside it.
+__device__ inline void list_pair(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery& Q,
+                                 uint64_t p0, uint32_t lane, uint64_t ws, uint64_t we, uint2& a, uint2& b, bool& m0,
+                                 bool& m1, bool& poison) {
+    const uint64_t e0 = p0 + 2ull * lane;
+    const bool v0 = e0 >= ws && e0 < we, v1 = e0 + 1 >= ws && e0 + 1 < we;
+    m0 = m1 = poison = false;
+    a = b = make_uint2(0, 0);
+    if (v0 || v1) {
+        const uint4 w = *reinterpret_cast<const uint4*>(T + e0);
+        a = make_uint2(w.x, w.y);
+        b = make_uint2(w.z, w.w);
+        bool p = false;
+        if (v0) {
+            list_test(Q, keys, a, m0, p);
+            poison = p;
+        }
+        if (v1) {
+            list_test(Q, keys, b, m1, p);
+            poison = poison || p;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(LIST_THREADS)
+list_count(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,
+           const LItem* __restrict__ items, uint32_t tile, uint32_t* __restrict__ cnt, uint32_t* __restrict__ wcnt,
+           uint32_t* __restrict__ qpoison) {
+    __shared__ uint32_t wsum[LIST_WAVES];
+    __shared__ uint32_t wpoi[LIST_WAVES];
+    const LItem it = items[blockIdx.x];
+    const LQuery Q = qs[it.q];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quarter = tile / LIST_WAVES;
+    const uint64_t ia = Q.lo + (uint64_t)it.tile * tile, ib = min(ia + tile, Q.hi);
+    const uint64_t ws = min(ia + (uint64_t)wave * quarter, ib), we = min(ws + quarter, ib);
+    uint32_t c = 0;
+    bool anyp = false;
+    for (uint64_t p0 = ws & ~1ull; p0 < we; p0 += 128) {
+        uint2 a, b;
+        bool m0, m1, p;
+        list_pair(T, keys, Q, p0, lane, ws, we, a, b, m0, m1, p);
+        c += __popcll(__ballot(m0)) + __popcll(__ballot(m1));
+        const uint64_t bp = __ballot(p);
+        anyp = anyp || bp != 0ull;
+    }
+    if (lane == 0) {
+        wsum[wave] = c;
+        wpoi[wave] = anyp ? 1u : 0u;
+    }
+    __syncthreads();
+    if (threadIdx.x < LIST_WAVES) wcnt[(uint64_t)blockIdx.x * LIST_WAVES + threadIdx.x] = wsum[threadIdx.x];
+    if (threadIdx.x == 0) {
+        uint32_t s = 0, p = 0;
+        for (uint32_t w = 0; w < LIST_WAVES; ++w) {
+            s += wsum[w];
+            p |= wpoi[w];
+        }
+        cnt[blockIdx.x] = s;
+        // only a subject-filtered query reads it: a poisoned tuple among the tuples matching its
+        // namespace, object and relation may be a match the snapshot cannot see
+        if (p && Q.subj != ANY) atomicOr(qpoison + it.q, 1u);
+    }
+}
+
+// totals of the group's queries [g0, g0 + nq): the distance between their first items' bases
+__global__ void __launch_bounds__(256) list_totals(const uint64_t* __restrict__ base, const uint32_t* __restrict__ ioff,
+                                                   uint32_t g0, uint32_t nq, uint64_t* __restrict__ tot) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nq) tot[g0 + i] = base[ioff[i + 1]] - base[ioff[i]];
+}
+
+__global__ void __launch_bounds__(LIST_THREADS)
+list_emit(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,
+          const LItem* __restrict__ items, uint32_t tile, const uint32_t* __restrict__ cnt,
+          const uint32_t* __restrict__ wcnt, const uint64_t* __restrict__ base, const uint32_t* __restrict__ ioff,
+          uint32_t g0, const LWindow* __restrict__ wins, uint2* __restrict__ out, uint64_t out_n,
+          uint32_t* __restrict__ qpage_poison) {
+    const LItem it = items[blockIdx.x];
+    const LWindow W = wins[it.q];
+    if (W.whi <= W.wlo) return;
+    const uint64_t r0 = base[blockIdx.x] - base[ioff[it.q - g0]];        // rank of the item's first match
+    if (r0 + cnt[blockIdx.x] <= W.wlo || r0 >= W.whi) return;
+    const LQuery Q = qs[it.q];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quarter = tile / LIST_WAVES;
+    const uint64_t ia = Q.lo + (uint64_t)it.tile * tile, ib = min(ia + tile, Q.hi);
+    const uint64_t ws = min(ia + (uint64_t)wave * quarter, ib), we = min(ws + quarter, ib);
+    uint64_t r = r0;
+    for (uint32_t w = 0; w < wave; ++w) r += wcnt[(uint64_t)blockIdx.x * LIST_WAVES + w];
+    if (r + wcnt[(uint64_t)blockIdx.x * LIST_WAVES + wave] <= W.wlo) return;    // the wave's matches miss the window
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (uint64_t p0 = ws & ~1ull; p0 < we && r < W.whi; p0 += 128) {
+        uint2 a, b;
+        bool m0, m1, p;
+        list_pair(T, keys, Q, p0, lane, ws, we, a, b, m0, m1, p);
+        const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
+        const uint64_t k0 = r + __popcll(b0 & below) + __popcll(b1 & below), k1 = k0 + (m0 ? 1u : 0u);
+        if (m0 && k0 >= W.wlo && k0 < W.whi) {
+            const uint64_t at = W.off + (k0 - W.wlo);
+            if (at < out_n) out[at] = a;
+            if (a.y == EDGE_POISON) atomicOr(qpage_poison + it.q, 1u);
+        }
+        if (m1 && k1 >= W.wlo && k1 < W.whi) {
+            const uint64_t at = W.off + (k1 - W.wlo);
+            if (at < out_n) out[at] = b;
+            if (b.y == EDGE_POISON) atomicOr(qpage_poison + it.q, 1u);
+        }
+        r += __popcll(b0) + __popcll(b1);
+    }
+}
+
+uint32_t list_tile() {
+    const char* e = getenv("KETO_LIST_TILE");
+    if (!e) return 4096;
+    const long v = atol(e);
+    if (v < 256 || v > (1l << 20) || v % 256 != 0)
+        throw Error{KETO_E_INVALID, "KETO_LIST_TILE must be a multiple of 256 in [256, 2^20]"};
+    return (uint32_t)v;
+}
+
+}  // namespace
+
+struct ListState {
+    // host part (any snapshot): the tuple rows in key order and their first entries
+    bool host_built = false;
+    uint64_t version = ~0ull;
+    std::vector<uint32_t> ord;
+    std::vector<uint64_t> first;     // ord.size() + 1
+    // device part
+    int device = -1;
+    bool dev_built = false;
+    uint2* T = nullptr;
+    uint2* keys = nullptr;
+    uint64_t bytes = 0;
+    float build_ms = 0;
+    hipStream_t stream = nullptr;
+    LBuf qs, items, ioff, cnt, wcnt, base, tot, qpoison, qpage, wins, out, tmp;
+    void free_index() {
+        if (T) (void)hipFree(T);
+        if (keys) (void)hipFree(keys);
+        T = keys = nullptr;
+        bytes = 0;
+        dev_built = false;
+    }
+    ~ListState() {
+        if (device < 0) return;
+        (void)hipSetDevice(device);
+        free_index();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+void ListStateDeleter::operator()(ListState* l) const { delete l; }
+
+uint64_t list_device_bytes(ListCache& C) {
+    std::lock_guard<std::mutex> lk(C.mu);
+    return C.state ? C.state->bytes : 0;
+}
+
+namespace {
+
+// the caller holds C.mu and S.rw shared
+ListState& host_index(const Snapshot& S, ListCache& C) {
+    if (!C.state) C.state.reset(new ListState);
+    ListState& L = *C.state;
+    const uint64_t ver = S.version.load();
+    if (L.host_built && L.version == ver) return L;
+    L.host_built = false;
+    L.dev_built = false;                       // the device tables follow on the next list_batch
+    L.ord = S.rows_in_key_order(RowKey{ANY_NS, ANY, ANY});
+    const uint64_t m = L.ord.size();
+    L.first.assign(m + 1, 0);
+    const unsigned th = m >= par_min() ? build_threads() : 1u;
+    par_chunks(m, th, 1 << 14, [&](uint64_t b, uint64_t e, unsigned) {
+        for (uint64_t i = b; i < e; ++i) L.first[i + 1] = S.row_edges(L.ord[i]).second;
+    });
+    for (uint64_t i = 0; i < m; ++i) L.first[i + 1] += L.first[i];
+    L.version = ver;
+    L.host_built = true;
+    return L;
+}
+
+// T and keys of the current host index, filled on host threads into pinned staging and uploaded
+void device_index(const Snapshot& S, ListState& L, int device) {
+    const auto t0 = std::chrono::steady_clock::now();
+    L.device = device;
+    L.free_index();
+    if (!L.stream) HIP_OK(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+    const uint64_t N = L.first.back(), R = S.n_rows(), m = L.ord.size();
+    const uint64_t t_entries = (N + 2) & ~1ull;                       // even, and never empty
+    HIP_OK(hipMalloc((void**)&L.T, t_entries * sizeof(uint2)));
+    HIP_OK(hipMalloc((void**)&L.keys, std::max<uint64_t>(R, 1) * sizeof(uint2)));
+    L.bytes = t_entries * sizeof(uint2) + std::max<uint64_t>(R, 1) * sizeof(uint2);
+    HIP_OK(hipMemsetAsync(L.T + N, 0, (t_entries - N) * sizeof(uint2), L.stream));
+    const unsigned th = std::max(N, R) >= par_min() ? build_threads() : 1u;
+    constexpr uint64_t CHUNK = 1ull << 22;                            // entries per staging block (32 MB)
+    struct Staging {
+        void* p;
+        explicit Staging(uint64_t bytes) : p(pinned_take(bytes)) {}
+        ~Staging() { pinned_give(p); }
+    } stage(std::min<uint64_t>(CHUNK, std::max<uint64_t>(std::max(N, R), 1)) * sizeof(uint2));
+    uint2* h = static_cast<uint2*>(stage.p);
+    for (uint64_t c0 = 0; c0 < R; c0 += CHUNK) {
+        const uint64_t c1 = std::min(R, c0 + CHUNK);
+        par_chunks(c1 - c0, th, 1 << 16, [&](uint64_t b, uint64_t e, unsigned) {
+            for (uint64_t r = c0 + b; r < c0 + e; ++r) h[r - c0] = make_uint2(S.row_key[r].obj, S.row_key[r].rel);
+        });
+        HIP_OK(hipMemcpyAsync(L.keys + c0, h, (c1 - c0) * sizeof(uint2), hipMemcpyHostToDevice, L.stream));
+        HIP_OK(hipStreamSynchronize(L.stream));
+    }
+    for (uint64_t c0 = 0; c0 < N; c0 += CHUNK) {
+        const uint64_t c1 = std::min(N, c0 + CHUNK);
+        par_chunks(c1 - c0, th, 1 << 16, [&](uint64_t b, uint64_t e, unsigned) {
+            uint64_t at = c0 + b;
+            const uint64_t end = c0 + e;
+            // the row holding entry `at`: the last one whose first entry is at or before it
+            uint64_t i = (uint64_t)(std::upper_bound(L.first.begin(), L.first.begin() + m + 1, at) - L.first.begin()) - 1;
+            while (at < end) {
+                const uint32_t row = L.ord[i];
+                const auto ed = S.row_edges(row);
+                const uint64_t stop = std::min(end, L.first[i + 1]);
+                for (uint64_t k = at - L.first[i]; at < stop; ++at, ++k) h[at - c0] = make_uint2(row, ed.first[k]);
+                ++i;
+            }
+        });
+        HIP_OK(hipMemcpyAsync(L.T + c0, h, (c1 - c0) * sizeof(uint2), hipMemcpyHostToDevice, L.stream));
+        HIP_OK(hipStreamSynchronize(L.stream));
+    }
+    HIP_OK(hipStreamSynchronize(L.stream));
+    L.dev_built = true;
+    L.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct Plan {
+    LQuery q{0, 0, ANY, ANY, ANY, 0};
+    int64_t ns = ANY_NS;
+    uint8_t status = KETO_LIST_OK;
+};
+
+// whereQuery + whereSubject against the host tables: statuses, the entry range and the predicates
+Plan resolve_list(const Snapshot& S, const ListState& L, const keto_list_req& rq) {
+    Plan P;
+    const std::string_view ns = sv(rq.namespace_), obj = sv(rq.object), rel = sv(rq.relation);
+    if (!ns.empty()) {
+        const int c = S.ns_index(ns);
+        if (c < 0) {                                     // GetNamespaceByName (:180)
+            P.status = KETO_LIST_NOT_FOUND;
+            return P;
+        }
+        P.ns = S.ns_ids[c];
+    }
+    RowKey sk{ANY_NS, ANY, ANY};                          // a subject set's row key
+    if (rq.has_subject && rq.subject.kind != 0) {
+        const std::string_view sn = sv(rq.subject.set_namespace);
+        const int c = S.ns_index(sn);
+        if (c < 0) {                                     // GetNamespaceByName (:161), "" included
+            P.status = KETO_LIST_NOT_FOUND;
+            return P;
+        }
+        sk.ns = sn.empty() ? ANY_NS : (int64_t)S.ns_ids[c];   // as the builder keys the target row
+    }
+    bool empty = false;
+    uint32_t o = ANY, r = ANY;
+    if (!obj.empty()) {
+        const int64_t x = S.lookup_str(obj);
+        if (x < 0) empty = true;
+        o = (uint32_t)x;
+    }
+    if (!rel.empty()) {
+        const int64_t x = S.lookup_str(rel);
+        if (x < 0) empty = true;
+        r = (uint32_t)x;
+    }
+    if (rq.has_subject && !empty) {
+        if (rq.subject.kind == 0) {
+            const int64_t x = S.lookup_str(sv(rq.subject.id));
+            if (x < 0) empty = true;
+            P.q.subj = (uint32_t)x;
+        } else {
+            // an empty object / relation is stored as the target key's ANY field (snapshot.cpp)
+            const std::string_view so = sv(rq.subject.set_object), sr = sv(rq.subject.set_relation);
+            const int64_t xo = so.empty() ? -2 : S.lookup_str(so), xr = sr.empty() ? -2 : S.lookup_str(sr);
+            if (xo == -1 || xr == -1) empty = true;
+            else {
+                sk.obj = xo == -2 ? ANY : (uint32_t)xo;
+                sk.rel = xr == -2 ? ANY : (uint32_t)xr;
+                int64_t row = sk.ns != ANY_NS && sk.obj != ANY && sk.rel != ANY ? S.real_row(sk) : -1;
+                if (row < 0) {
+                    auto it = S.row_of.find(sk);
+                    if (it != S.row_of.end()) row = it->second;
+                }
+                if (row < 0) empty = true;               // no stored subject set names it
+                else P.q.subj = EDGE_SET | (uint32_t)row;
+            }
+        }
+    }
+    if (empty) return P;                                 // lo == hi == 0
+    // the entry range: binary searches over the tuple rows in key order
+    uint64_t p0 = 0, p1 = L.ord.size();
+    if (P.ns != ANY_NS) {
+        auto lo = std::lower_bound(L.ord.begin(), L.ord.end(), P.ns, [&](uint32_t row, int64_t v) { return S.row_key[row].ns < v; });
+        auto hi = std::upper_bound(lo, L.ord.end(), P.ns, [&](int64_t v, uint32_t row) { return v < S.row_key[row].ns; });
+        p0 = lo - L.ord.begin();
+        p1 = hi - L.ord.begin();
+        if (o != ANY) {
+            auto b = L.ord.begin() + p0, e = L.ord.begin() + p1;
+            auto lo2 = std::lower_bound(b, e, o, [&](uint32_t row, uint32_t v) { return S.str_cmp(S.row_key[row].obj, v) < 0; });
+            auto hi2 = std::upper_bound(lo2, e, o, [&](uint32_t v, uint32_t row) { return S.str_cmp(v, S.row_key[row].obj) < 0; });
+            p0 = lo2 - L.ord.begin();
+            p1 = hi2 - L.ord.begin();
+            if (r != ANY) {
+                auto b3 = L.ord.begin() + p0, e3 = L.ord.begin() + p1;
+                auto lo3 = std::lower_bound(b3, e3, r, [&](uint32_t row, uint32_t v) { return S.str_cmp(S.row_key[row].rel, v) < 0; });
+                auto hi3 = std::upper_bound(lo3, e3, r, [&](uint32_t v, uint32_t row) { return S.str_cmp(v, S.row_key[row].rel) < 0; });
+                p0 = lo3 - L.ord.begin();
+                p1 = hi3 - L.ord.begin();
+            }
+        } else if (r != ANY) {
+            P.q.rel = r;
+        }
+    } else {
+        P.q.obj = o;
+        P.q.rel = r;
+    }
+    P.q.lo = L.first[p0];
+    P.q.hi = L.first[p1];
+    if (P.q.lo == P.q.hi) P.q.lo = P.q.hi = 0, P.q.obj = P.q.rel = ANY;
+    return P;
+}
+
+}  // namespace
+
+void list_plan(const Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, keto_list_plan_t* out) {
+    const ListState* L;
+    {
+        std::lock_guard<std::mutex> lk(C.mu);
+        L = &host_index(S, C);
+    }
+    // the index of this version is not rebuilt while the caller holds the snapshot's lock shared
+    const unsigned th = n >= 4096 ? build_threads() : 1u;
+    par_chunks(n, th, 1024, [&](uint64_t b, uint64_t e, unsigned) {
+        for (uint64_t i = b; i < e; ++i) {
+            const Plan P = resolve_list(S, *L, reqs[i]);
+            out[i] = keto_list_plan_t{P.q.lo, P.q.hi, P.ns, P.q.obj, P.q.rel, P.q.subj, P.status};
+        }
+    });
+}
+
+void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, ListResult& out) {
+    if (S.n_parts > 1) throw Error{KETO_E_INVALID, "keto_list_batch: a part of a partitioned snapshot holds only some rows"};
+    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
+    out.status.assign(n, KETO_LIST_OK);
+    out.offsets.assign((uint64_t)n + 1, 0);
+    out.next_page.assign(n, 0);
+    out.totals.assign(n, 0);
+    out.tuples = nullptr;
+    out.index_ms = out.scan_ms = 0;
+    if (n == 0) return;
+    const uint32_t tile = list_tile();
+    std::lock_guard<std::mutex> lk(C.mu);                    // one list call at a time per snapshot
+    HIP_OK(hipSetDevice(V.device));
+    ListState& L = host_index(S, C);
+    if (!L.dev_built) {
+        device_index(S, L, V.device);
+        out.index_ms = L.build_ms;
+    }
+    hipStream_t st = L.stream;
+
+    // ---- resolve (host threads)
+    std::vector<LQuery> qs(n);
+    const unsigned th = n >= 4096 ? build_threads() : 1u;
+    par_chunks(n, th, 1024, [&](uint64_t b, uint64_t e, unsigned) {
+        for (uint64_t i = b; i < e; ++i) {
+            const Plan P = resolve_list(S, L, reqs[i]);
+            qs[i] = P.q;
+            out.status[i] = P.status;
+        }
+    });
+    // items per query, and the query groups of at most LIST_GROUP_ITEMS items (a single query may exceed it)
+    std::vector<uint64_t> qitems((uint64_t)n + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t k = (qs[i].hi - qs[i].lo + tile - 1) / tile;
+        if (k > 0xFFFFFFF0ull) throw Error{KETO_E_RANGE, "keto_list_batch: a query spans more than 2^32 tiles"};
+        qitems[i + 1] = qitems[i] + k;
+    }
+    std::vector<uint32_t> groups{0};
+    for (uint32_t i = 0; i < n; ++i)
+        if (qitems[i + 1] - qitems[groups.back()] > LIST_GROUP_ITEMS && i > groups.back()) groups.push_back(i);
+    groups.push_back(n);
+    for (size_t g = 0; g + 1 < groups.size(); ++g)
+        if (qitems[groups[g + 1]] - qitems[groups[g]] > 0xFFFFFFF0ull)
+            throw Error{KETO_E_RANGE, "keto_list_batch: a query spans more than 2^32 tiles"};
+
+    LQuery* d_qs = L.qs.get<LQuery>(n);
+    uint64_t* d_tot = L.tot.get<uint64_t>(n);
+    uint32_t* d_qpoison = L.qpoison.get<uint32_t>(n);
+    uint32_t* d_qpage = L.qpage.get<uint32_t>(n);
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    struct Events {
+        hipEvent_t a, b;
+        ~Events() {
+            (void)hipEventDestroy(a);
+            (void)hipEventDestroy(b);
+        }
+    } events{e0, e1};
+    HIP_OK(hipEventRecord(e0, st));
+    HIP_OK(hipMemcpyAsync(d_qs, qs.data(), (uint64_t)n * sizeof(LQuery), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_tot, 0, (uint64_t)n * sizeof(uint64_t), st));
+    HIP_OK(hipMemsetAsync(d_qpoison, 0, (uint64_t)n * sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(d_qpage, 0, (uint64_t)n * sizeof(uint32_t), st));
+
+    // the count pass of one query group: its items, their counts, the scanned bases and the totals;
+    // returns the group's item count (the buffers hold one group at a time)
+    std::vector<LItem> items;
+    std::vector<uint32_t> ioff;
+    const bool one_group = groups.size() == 2;
+    auto count_group = [&](uint32_t g0, uint32_t g1) -> uint32_t {
+        const uint32_t m = (uint32_t)(qitems[g1] - qitems[g0]);
+        if (m == 0) return 0;
+        items.resize(m);
+        ioff.resize((uint64_t)(g1 - g0) + 1);
+        for (uint32_t q = g0; q < g1; ++q) {
+            const uint64_t at = qitems[q] - qitems[g0], k = qitems[q + 1] - qitems[q];
+            ioff[q - g0] = (uint32_t)at;
+            for (uint64_t t = 0; t < k; ++t) items[at + t] = LItem{q, (uint32_t)t};
+        }
+        ioff[g1 - g0] = m;
+        LItem* d_items = L.items.get<LItem>(m);
+        uint32_t* d_ioff = L.ioff.get<uint32_t>(ioff.size());
+        uint32_t* d_cnt = L.cnt.get<uint32_t>((uint64_t)m + 1);
+        uint32_t* d_wcnt = L.wcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
+        uint64_t* d_base = L.base.get<uint64_t>((uint64_t)m + 1);
+        HIP_OK(hipMemcpyAsync(d_items, items.data(), (uint64_t)m * sizeof(LItem), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_ioff, ioff.data(), ioff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemsetAsync(d_cnt + m, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(list_count, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, d_items, tile, d_cnt, d_wcnt,
+                           d_qpoison);
+        HIP_OK(hipGetLastError());
+        struct Widen {
+            __host__ __device__ uint64_t operator()(uint32_t c) const { return c; }
+        };
+        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> cit(d_cnt, Widen{});
+        size_t tb = 0;
+        HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cit, d_base, (uint64_t)m + 1, st));
+        void* tmp = L.tmp.get<uint8_t>(tb);
+        HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cit, d_base, (uint64_t)m + 1, st));
+        hipLaunchKernelGGL(list_totals, dim3((g1 - g0 + 255) / 256), dim3(256), 0, st, d_base, d_ioff, g0, g1 - g0, d_tot);
+        HIP_OK(hipGetLastError());
+        // several groups share `items` / `ioff`: the copies above must have read them before the next refill
+        if (!one_group) HIP_OK(hipStreamSynchronize(st));
+        return m;
+    };
+    uint32_t m_last = 0;
+    for (size_t g = 0; g + 1 < groups.size(); ++g) m_last = count_group(groups[g], groups[g + 1]);
+
+    // ---- the one host sync between the passes: totals -> sizes, statuses, tokens
+    std::vector<uint64_t> tot(n);
+    std::vector<uint32_t> qpoison(n);
+    HIP_OK(hipMemcpyAsync(tot.data(), d_tot, (uint64_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(qpoison.data(), d_qpoison, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    std::vector<LWindow> wins(n);
+    uint64_t total_out = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        wins[i] = LWindow{0, 0, total_out};
+        if (out.status[i] != KETO_LIST_OK) continue;
+        if (qs[i].subj != ANY && qpoison[i]) {
+            out.status[i] = KETO_LIST_UNDECIDED;
+            continue;
+        }
+        const uint64_t size = reqs[i].page_size ? reqs[i].page_size : S.page_size;
+        const uint64_t page = std::max<uint32_t>(reqs[i].page, 1u);
+        const uint64_t first = (page - 1) * size;                       // < 2^63
+        const uint64_t k = tot[i] > first ? std::min(size, tot[i] - first) : 0;
+        out.totals[i] = tot[i];
+        out.next_page[i] = page >= (tot[i] + size - 1) / size ? 0 : page + 1;
+        wins[i].wlo = first;
+        wins[i].whi = first + k;
+        total_out += k;
+    }
+    std::vector<uint32_t> qpage(n, 0);
+    struct Block {                                          // the result's pinned block until it is handed over
+        void* p = nullptr;
+        ~Block() { pinned_give(p); }
+    } block;
+    if (total_out) {
+        LWindow* d_wins = L.wins.get<LWindow>(n);
+        uint2* d_out = L.out.get<uint2>(total_out);
+        HIP_OK(hipMemcpyAsync(d_wins, wins.data(), (uint64_t)n * sizeof(LWindow), hipMemcpyHostToDevice, st));
+        for (size_t g = 0; g + 1 < groups.size(); ++g) {
+            const uint32_t m = one_group ? m_last : count_group(groups[g], groups[g + 1]);
+            if (m == 0) continue;
+            hipLaunchKernelGGL(list_emit, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, (const LItem*)L.items.p, tile,
+                               (const uint32_t*)L.cnt.p, (const uint32_t*)L.wcnt.p, (const uint64_t*)L.base.p,
+                               (const uint32_t*)L.ioff.p, groups[g], d_wins, d_out, total_out, d_qpage);
+            HIP_OK(hipGetLastError());
+        }
+        block.p = pinned_take(total_out * sizeof(keto_list_tuple));
+        static_assert(sizeof(keto_list_tuple) == sizeof(uint2), "a list tuple is an index entry");
+        HIP_OK(hipMemcpyAsync(block.p, d_out, total_out * sizeof(uint2), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(qpage.data(), d_qpage, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipEventRecord(e1, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipEventElapsedTime(&out.scan_ms, e0, e1));
+
+    // ---- offsets; a page holding a poisoned tuple fails as a whole (toInternal over the page)
+    keto_list_tuple* tup = static_cast<keto_list_tuple*>(block.p);
+    uint64_t w = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t k = wins[i].whi - wins[i].wlo, from = wins[i].off;
+        out.offsets[i] = w;
+        if (k && qpage[i]) {
+            out.status[i] = KETO_LIST_NOT_FOUND;
+            out.totals[i] = 0;
+            out.next_page[i] = 0;
+            continue;
+        }
+        if (k && w != from) std::memmove(tup + w, tup + from, k * sizeof(keto_list_tuple));
+        w += k;
+    }
+    out.offsets[n] = w;
+    out.tuples = tup;
+    block.p = nullptr;
+}
+
+}  // namespace keto
