@@ -225,6 +225,13 @@ def test_engine_build_id_keys_traffic_profiles(tmp_path, monkeypatch):
     assert build.engine_build_id() == want
 
 
+def test_build_sources_exist():
+    """Every unit build.py compiles is in csrc, and per-source flags name only such units."""
+    from keto_amd import build
+    assert all(os.path.isfile(os.path.join(build.CSRC, s)) for s in build.SOURCES)
+    assert len(set(build.SOURCES)) == len(build.SOURCES) and set(build.SOURCE_FLAGS) <= set(build.SOURCES)
+
+
 def test_check_kernel_names(monkeypatch):
     """keto_check_kernel_name reads no device: the tier-0 instance a depth and the environment pick,
     by name (the name column of engine.hip's T0_TABLE)."""
