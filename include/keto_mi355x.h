@@ -229,7 +229,7 @@ int keto_snapshot_load(const char* path, int32_t device, keto_snapshot** out, ui
  * (internal/check/handler.go:182). */
 int keto_snapshot_apply(keto_snapshot* s, const keto_tuple* inserts, uint64_t n_inserts, const keto_tuple* deletes,
                         uint64_t n_deletes, uint64_t* version_out);
-/* Version of the snapshot: 0 after the build, +1 per keto_snapshot_apply. */
+/* Version of the snapshot: 0 after the build, +1 per keto_snapshot_apply or keto_snapshot_delete_query. */
 uint64_t keto_snapshot_version(const keto_snapshot* s);
 
 /* Edge-partitioned upload, for graphs larger than one GPU (one process per GPU, n_parts parts).
@@ -652,7 +652,8 @@ const uint8_t* keto_encoded_status(const keto_encoded* e);             /* n x KE
  *
  * The first list call on a snapshot version builds the list index on host threads and uploads it
  * (8 B per tuple plus 8 B per row of device memory, counted in keto_snapshot_stats.device_bytes); a
- * write invalidates it and the next list call rebuilds all of it (no incremental patching).
+ * keto_snapshot_apply invalidates it and the next list call rebuilds all of it; a
+ * keto_snapshot_delete_query patches it to the new version (below).
  * Errors: a host-only snapshot is KETO_E_HIP, any part of a partitioned upload (n_parts > 1)
  * KETO_E_INVALID; n = 0 gives count 0 and offsets {0}.  Calls take the snapshot's lock shared, as
  * keto_expand_batch does, and run one at a time per snapshot. */
@@ -691,6 +692,53 @@ int keto_listed_timing(const keto_listed*, float* index_ms, float* scan_ms);
  * compares it); status = KETO_LIST_OK or KETO_LIST_NOT_FOUND (unknown namespace). */
 typedef struct { uint64_t lo, hi; int64_t ns; uint32_t obj, rel, subject; uint8_t status; } keto_list_plan_t;
 int keto_list_plan(const keto_snapshot* s, const keto_list_req* reqs, uint32_t n, keto_list_plan_t* out);
+
+/* ---- Delete by query: DeleteAllRelationTuples on a live snapshot (repo:keto_amd/csrc/list.hip, delta.cpp) ----
+ * keto_snapshot_delete_query follows relationtuple.Manager.DeleteAllRelationTuples
+ * (internal/relationtuple/definitions.go:28-34), i.e. sql.(*Persister).DeleteAllRelationTuples
+ * (internal/persistence/sql/relationtuples.go:225-236): the delete behind DELETE /relation-tuples
+ * (internal/relationtuple/transact_server.go:187-208) and the gRPC DeleteRelationTuples (:55-70).  Every
+ * tuple matching whereQuery (:178-198) and, for a subject, whereSubject (:151-176: typed, exact on
+ * every field) is removed, duplicates included; an empty query removes every tuple.  `query` is a
+ * keto_list_req whose page_size and page are ignored.  A filter naming a string or subject the snapshot
+ * has never seen matches nothing (KETO_OK, deleted = 0).  An unknown query namespace or subject-set
+ * namespace ("" included, as for lists) fails the call with KETO_E_INVALID and changes nothing, as
+ * GetNamespaceByName fails the reference's transaction (:161,180).  Materialized wildcard rows are
+ * views: never matched themselves, re-materialized when a row their query returns lost a tuple; a
+ * stored subject set with an empty field is a tuple, matched by its subject word as in a list.
+ *
+ * Every successful call bumps the version by 1, like keto_snapshot_apply, also when nothing matched:
+ * replicas and parts given the same calls stay at equal versions.  A shared-rows part and a host-only
+ * snapshot take the call; a migrating part takes none (KETO_E_INVALID).  Locking is
+ * keto_snapshot_apply's: the scan and the staging run under the shared lock (batches keep running), the
+ * commit under the exclusive one.
+ *
+ * KETO_E_REBUILD (snapshot unchanged: same version, same answers; the caller rebuilds): a matched tuple
+ * is a poisoned one; the query has a subject and a poisoned tuple lies among the tuples matching its
+ * namespace / object / relation part (the list call's KETO_LIST_UNDECIDED rule); a touched row, or a
+ * wildcard row matching one, is poisoned; or more than KETO_DELETE_QUERY_MAX_ROWS rows (environment,
+ * default 2^20) are touched -- every touched row is re-imaged on the device, so past some size a rebuild
+ * is the cheaper answer.
+ *
+ * Who finds the rows: the host (candidate rows by the resolver's binary searches, scanned on host
+ * threads) on a host-only snapshot, a part, when the device list index is not current at this version
+ * -- a delete never builds it -- or when namespace, object and relation are all given (one row); the
+ * device (a count / scan / emit pass over the list index, as in keto_list_batch) otherwise.  A device
+ * list index that was current is patched out of place to the new version (8 B less per deleted tuple)
+ * instead of being rebuilt by the next list call; if the patch fails the index is dropped and the next
+ * list call rebuilds it -- the delete has happened either way. */
+#define KETO_DELETE_PATH_HOST 0
+#define KETO_DELETE_PATH_DEVICE 1
+typedef struct {
+    uint64_t deleted;       /* tuples removed (SQL: rows affected) */
+    uint64_t rows_touched;  /* distinct (namespace_id, object, relation) rows that lost a tuple */
+    uint64_t version;       /* the snapshot's version after the call */
+    uint32_t path;          /* KETO_DELETE_PATH_HOST | KETO_DELETE_PATH_DEVICE: who found the rows */
+    uint32_t index_kept;    /* 1 = the device list index was patched and is current at `version` */
+    float    scan_ms;       /* finding the rows (host wall time, or HIP events on the list stream) */
+    float    apply_ms;      /* staging + commit + device_apply, and the index patch */
+} keto_delete_info;
+int keto_snapshot_delete_query(keto_snapshot* s, const keto_list_req* query, keto_delete_info* out /* may be NULL */);
 
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,

@@ -93,8 +93,23 @@ type gpuState struct {
 
 	wmu        sync.Mutex // one write transaction (SQL commit + Apply) at a time; the rebuild's scan holds it too
 	rebuilding bool
-	pending    [][2][]gpu.Row // writes committed after the rebuild's scan, applied to the new snapshot
+	pending    []pendingWrite // writes committed after the rebuild's scan, applied to the new snapshot in commit order
 	rescan     bool           // a write during the rebuild cannot be replayed: scan the table again
+}
+
+// pendingWrite is one committed write a running rebuild has to replay: a transaction's rows, or a
+// delete by query.
+type pendingWrite struct {
+	ins, del []gpu.Row
+	query    *gpu.ListQuery // non-nil: DeleteAllRelationTuples
+}
+
+// replay applies the write to a set of engines.
+func (w pendingWrite) replay(engines []gpu.Engine) error {
+	if w.query != nil {
+		return gpu.DeleteQueryEngines(engines, *w.query)
+	}
+	return gpu.ApplyEngines(engines, w.ins, w.del)
 }
 
 // one state per registry (RegistryDefault's fields are in registry_default.go)
@@ -254,7 +269,7 @@ func (g *gpuState) applyLocked(ctx context.Context, ins, del []*relationtuple.In
 			g.rescan = true
 			return
 		}
-		g.pending = append(g.pending, [2][]gpu.Row{iRows, dRows})
+		g.pending = append(g.pending, pendingWrite{ins: iRows, del: dRows})
 		return
 	}
 	g.mu.RLock()
@@ -324,7 +339,7 @@ func (g *gpuState) rebuild() {
 		}
 		replayed := true
 		for _, w := range g.pending {
-			if gpu.ApplyEngines(engines, w[0], w[1]) != nil {
+			if w.replay(engines) != nil {
 				replayed = false
 				break
 			}
@@ -384,18 +399,35 @@ func (p *gpuPersister) TransactRelationTuples(ctx context.Context, ins, del []*r
 	return nil
 }
 
-// DeleteAllRelationTuples deletes by query (whereQuery, relationtuples.go:178-198): the rows are not
-// named, so the snapshot is rebuilt from the table.
+// DeleteAllRelationTuples deletes by query (whereQuery, relationtuples.go:178-198).  After the SQL
+// delete committed the engines take the same query (keto_snapshot_delete_query finds the rows); the
+// set goes stale and is rebuilt only on an error (gpu.ErrRebuild: a poisoned tuple among the
+// matches, or more touched rows than the cap).  While a rebuild is running the query is queued with
+// the transactions, in commit order, and replayed on the new snapshot.
 func (p *gpuPersister) DeleteAllRelationTuples(ctx context.Context, q *relationtuple.RelationQuery) error {
 	p.g.wmu.Lock()
 	defer p.g.wmu.Unlock()
 	if err := p.Persister.DeleteAllRelationTuples(ctx, q); err != nil {
 		return err
 	}
-	if p.g.rebuilding {
-		p.g.rescan = true
-		return nil
-	}
-	p.g.startRebuildLocked()
+	p.g.deleteQueryLocked(gpu.ListQuery{Namespace: q.Namespace, Object: q.Object, Relation: q.Relation, Subject: q.Subject()})
 	return nil
+}
+
+// deleteQueryLocked runs after a delete by query committed, with wmu held (see applyLocked).
+func (g *gpuState) deleteQueryLocked(q gpu.ListQuery) {
+	if g.rebuilding {
+		g.pending = append(g.pending, pendingWrite{query: &q})
+		return
+	}
+	g.mu.RLock()
+	engines, stale := g.engines, g.stale
+	g.mu.RUnlock()
+	if stale { // an earlier rebuild failed: the replicas are behind, try again
+		g.startRebuildLocked()
+		return
+	}
+	if err := gpu.DeleteQueryEngines(engines, q); err != nil {
+		g.startRebuildLocked()
+	}
 }

@@ -23,6 +23,7 @@ type Engine interface {
 	CheckBatch(reqs []*relationtuple.InternalRelationTuple, depths []int, globalMax int) ([]bool, []uint8, error)
 	ExpandBatch(subs []relationtuple.Subject, depths []int, globalMax int) ([][]Node, []error, error)
 	Apply(inserts, deletes []Row) error
+	DeleteQuery(q ListQuery) (DeleteInfo, error)
 	Footprint() map[int]uint64
 	Close()
 }
@@ -287,6 +288,24 @@ func (p *Partition) Apply(inserts, deletes []Row) error {
 	return firstErr(p.ranks(func(k int) error { return p.parts[k].Apply(inserts, deletes) }))
 }
 
+// DeleteQuery follows one committed delete by query on every part (see Snapshot.DeleteQuery): each
+// part's host tables are the whole graph's, so each finds the same rows and reports the same counts;
+// the first part's are returned.  An error leaves the parts inconsistent: the caller rebuilds.
+func (p *Partition) DeleteQuery(q ListQuery) (DeleteInfo, error) {
+	p.mu.Lock()
+	defer p.mu.Unlock()
+	infos := make([]DeleteInfo, len(p.parts))
+	err := firstErr(p.ranks(func(k int) error {
+		var e error
+		infos[k], e = p.parts[k].DeleteQuery(q)
+		return e
+	}))
+	if err != nil || len(infos) == 0 {
+		return DeleteInfo{}, err
+	}
+	return infos[0], nil
+}
+
 // Close releases the communicators and the parts.
 func (p *Partition) Close() {
 	for _, c := range p.comms {
@@ -435,6 +454,17 @@ func PlaceWith(base *Snapshot, devices []int, mode string, resident map[int]uint
 func ApplyEngines(es []Engine, inserts, deletes []Row) error {
 	for _, e := range es {
 		if err := e.Apply(inserts, deletes); err != nil {
+			return err
+		}
+	}
+	return nil
+}
+
+// DeleteQueryEngines applies one delete by query to every engine of a set (see
+// Snapshot.DeleteQuery).  An error leaves the set inconsistent: the caller rebuilds it.
+func DeleteQueryEngines(es []Engine, q ListQuery) error {
+	for _, e := range es {
+		if _, err := e.DeleteQuery(q); err != nil {
 			return err
 		}
 	}

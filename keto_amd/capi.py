@@ -46,7 +46,9 @@ EXPORTS = [
     "keto_encoded_bytes", "keto_encoded_offsets", "keto_encoded_status",
     "keto_list_batch", "keto_listed_free", "keto_listed_count", "keto_listed_tuples", "keto_listed_offsets",
     "keto_listed_status", "keto_listed_next_page", "keto_listed_totals", "keto_listed_timing", "keto_list_plan",
+    "keto_snapshot_delete_query",
 ]
+DELETE_PATH_HOST, DELETE_PATH_DEVICE = 0, 1
 LIST_OK, LIST_NOT_FOUND, LIST_UNDECIDED = 0, 1, 2
 ENC_PROTO, ENC_JSON = 0, 1
 ENCODINGS = {"proto": ENC_PROTO, "json": ENC_JSON}
@@ -136,6 +138,11 @@ class KListReq(C.Structure):
 class KListPlan(C.Structure):
     _fields_ = [("lo", C.c_uint64), ("hi", C.c_uint64), ("ns", C.c_int64), ("obj", C.c_uint32), ("rel", C.c_uint32),
                 ("subject", C.c_uint32), ("status", C.c_uint8)]
+
+
+class KDeleteInfo(C.Structure):
+    _fields_ = [("deleted", C.c_uint64), ("rows_touched", C.c_uint64), ("version", C.c_uint64), ("path", C.c_uint32),
+                ("index_kept", C.c_uint32), ("scan_ms", C.c_float), ("apply_ms", C.c_float)]
 
 
 LIST_TUPLE_DTYPE = np.dtype([("row", "<u4"), ("subject", "<u4")])
@@ -367,6 +374,18 @@ class Snapshot:
         _check(self.lib.keto_snapshot_apply(self.h, self._tuples(keep, ins), C.c_uint64(len(ins)),
                                             self._tuples(keep, dels), C.c_uint64(len(dels)), C.byref(ver)))
         return ver.value
+
+    def delete_query(self, namespace="", object="", relation="", subject=None) -> dict:
+        """keto_snapshot_delete_query: DeleteAllRelationTuples -- every tuple matching the query leaves the
+        snapshot ("" = not filtered; subject as in check_batch, None = any).  Returns the keto_delete_info
+        fields.  Raises KetoError (code -6 = KETO_E_REBUILD: rebuild instead, the snapshot is unchanged)."""
+        keep = _Keep()
+        info = KDeleteInfo()
+        req = self._list_reqs(keep, [(namespace, object, relation, subject, 0, 0)])
+        _check(self.lib.keto_snapshot_delete_query(self.h, req, C.byref(info)))
+        return {"deleted": int(info.deleted), "rows_touched": int(info.rows_touched), "version": int(info.version),
+                "path": int(info.path), "index_kept": int(info.index_kept), "scan_ms": float(info.scan_ms),
+                "apply_ms": float(info.apply_ms)}
 
     def version(self) -> int:
         return int(self.lib.keto_snapshot_version(self.h))

@@ -11,6 +11,7 @@
 #include <thread>
 
 #include "capi_internal.hpp"
+#include "delta.hpp"
 #include "parallel.hpp"
 #include "snapshot.hpp"
 
@@ -649,6 +650,58 @@ int keto_snapshot_apply(keto_snapshot* h, const keto_tuple* inserts, uint64_t n_
                     std::chrono::duration<double, std::milli>(t2 - t1).count(),
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
         if (version_out) *version_out = S.version;
+        return KETO_OK;
+    });
+}
+
+int keto_snapshot_delete_query(keto_snapshot* h, const keto_list_req* query, keto_delete_info* out) {
+    return guarded([&] {
+        if (!h || !query) throw Error{KETO_E_INVALID, "NULL argument"};
+        Snapshot& S = *h->s;
+        // keto_snapshot_apply's locking: the scan and the staging under the shared lock, the commit
+        // under the exclusive one.  The scan takes the list index's mutex under the shared lock, as
+        // list calls do, and has released it before the commit waits for the exclusive lock; the
+        // patched index is installed under the exclusive lock, the mutex taken again
+        std::lock_guard<std::mutex> wl(S.apply_mu);
+        std::shared_lock<RwGate> rl(S.rw);
+        std::unique_lock<RwGate> xl(S.rw, std::defer_lock);
+        struct Retire {
+            Snapshot& S;
+            std::unique_lock<RwGate>& xl;
+            ~Retire() {
+                if (xl.owns_lock()) xl.unlock();
+                S.retired.clear();
+            }
+        } retire{S, xl};
+        if (S.part_mode == PART_MIGRATE && S.n_parts > 1)
+            throw Error{KETO_E_INVALID, "keto_snapshot_delete_query: a migrating part takes no writes"};
+        uint64_t max_rows = 1ull << 20;
+        if (const char* e = getenv("KETO_DELETE_QUERY_MAX_ROWS")) max_rows = (uint64_t)std::max(0ll, atoll(e));
+        DeleteScan sc;
+        delete_scan(S, h->list, *query, max_rows, sc);
+        if (sc.poisoned)
+            throw Error{KETO_E_REBUILD, "a delete by query matches, or may match, a poisoned tuple"};
+        if (sc.heads > max_rows)
+            throw Error{KETO_E_REBUILD, "a delete by query touches " + std::to_string(sc.heads) +
+                                            " rows, more than KETO_DELETE_QUERY_MAX_ROWS"};
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<RowErase> erase(sc.rows.size());
+        for (size_t i = 0; i < erase.size(); ++i) erase[i] = RowErase{sc.rows[i], sc.subject};
+        apply_writes_erase(S, nullptr, 0, nullptr, 0, erase.data(), erase.size(), [&] {
+            rl.unlock();
+            xl.lock();
+        });
+        if (!S.dirty.empty() || !S.needs_cb.empty()) device_apply(S);
+        const bool kept = delete_index_patch(S, h->list, sc);
+        if (out) {
+            out->deleted = sc.matches;
+            out->rows_touched = sc.rows.size();
+            out->version = S.version;
+            out->path = sc.path;
+            out->index_kept = kept ? 1u : 0u;
+            out->scan_ms = sc.scan_ms;
+            out->apply_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
         return KETO_OK;
     });
 }

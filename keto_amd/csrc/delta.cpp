@@ -25,12 +25,18 @@
 // edge-partitioned snapshot (KETO_PART_SHARED) takes every transaction: its host tables are the whole
 // graph's, and device_apply writes the rows the part holds (every subject-set target and its own root
 // rows); a migrating part takes none.
+//
+// keto_snapshot_delete_query (DeleteAllRelationTuples, relationtuples.go:225-236) commits through the
+// same stages: its scan (list.hip) names the rows a query touches, and apply_writes_erase stages them
+// as row-level erasures -- every edge equal to a subject word, or the whole row -- after the tuple
+// deletes.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 
+#include "delta.hpp"
 #include "parallel.hpp"
 #include "snapshot.hpp"
 
@@ -306,6 +312,11 @@ struct Grown {
 
 void apply_writes(Snapshot& S, const keto_tuple* ins, uint64_t n_ins, const keto_tuple* del, uint64_t n_del,
                   const std::function<void()>& commit) {
+    apply_writes_erase(S, ins, n_ins, del, n_del, nullptr, 0, commit);
+}
+
+void apply_writes_erase(Snapshot& S, const keto_tuple* ins, uint64_t n_ins, const keto_tuple* del, uint64_t n_del,
+                        const RowErase* erase, uint64_t n_erase, const std::function<void()>& commit) {
     // a part of an edge-partitioned snapshot holds the whole graph's host tables: every part applies
     // every transaction.  A shared-rows part writes the rows it holds in place (device_apply); a
     // migrating part's stubs carry their owners' handles and filters, which a write on the owner can
@@ -331,6 +342,16 @@ void apply_writes(Snapshot& S, const keto_tuple* ins, uint64_t n_ins, const keto
         if (r < 0) continue;
         std::vector<uint32_t>& e = T.edges((uint32_t)r);
         e.erase(std::remove(e.begin(), e.end(), v), e.end());
+    }
+    // ---- row-level erasures (DeleteAllRelationTuples, relationtuples.go:225-236: the rows a query's
+    // scan found): every edge equal to the subject word, or the whole row
+    if (n_erase && !erase) throw Error{KETO_E_INVALID, "NULL erasures"};
+    for (uint64_t i = 0; i < n_erase; ++i) {
+        if (erase[i].row >= S.n_rows() || wild_key(S.row_key[erase[i].row]))
+            throw Error{KETO_E_INVALID, "an erasure names no tuple row"};
+        std::vector<uint32_t>& e = T.edges(erase[i].row);
+        if (erase[i].subject == ANY) e.clear();
+        else e.erase(std::remove(e.begin(), e.end(), erase[i].subject), e.end());
     }
     // ---- Subject.String() collisions (graph_utils.go:13-35 keys) this transaction creates: a new row
     // whose String() is another subject's (a subject id -- conservatively, any existing string -- or

@@ -31,7 +31,17 @@
 // the passes (totals -> result sizes, statuses, tokens).
 //
 // Known limit: a write (keto_snapshot_apply) invalidates the whole index; the next list call
-// rebuilds and uploads all of it.  Patching it in place is not done.
+// rebuilds and uploads all of it.
+//
+// keto_snapshot_delete_query (DeleteAllRelationTuples, relationtuples.go:225-236) uses the same
+// resolver and, when the device index is current, the same passes to find the rows a query touches:
+// list_count_heads counts matches and heads (the first match of each row's run: one per touched row)
+// and flags poisoned tuples, list_emit_heads writes the heads' row ids.  After the commit a current
+// index follows the delete instead of going stale: a new T is built out of place from a copy of
+// [0, lo), list_emit_keep over [lo, hi) (the entries that do not match, each moved down by the matches
+// before it) and a copy of [hi, N); keys[] stays (a delete adds no row), ord / first are rebuilt on
+// the host.  Without a current device index the host scans the candidate rows ord[p0, p1) instead,
+// and no index is built for a delete.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -132,33 +142,63 @@ __device__ inline void list_pair(const uint2* __restrict__ T, const uint2* __res
     }
 }
 
-__global__ void __launch_bounds__(LIST_THREADS)
-list_count(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,
-           const LItem* __restrict__ items, uint32_t tile, uint32_t* __restrict__ cnt, uint32_t* __restrict__ wcnt,
-           uint32_t* __restrict__ qpoison) {
-    __shared__ uint32_t wsum[LIST_WAVES];
-    __shared__ uint32_t wpoi[LIST_WAVES];
+// What an entry has to be for a pass to count or emit it (a compile-time mode of the count and emit
+// bodies): MATCH -- the query's predicate (lists); HEAD -- a match that starts its row's run of
+// matches: entry i of [lo, hi) matches and (i == lo, or T[i-1] is another row's, or T[i-1] does not
+// match) -- key predicates hold for a whole row and equal subject words are adjacent in the ORDER BY,
+// so the matches of one row are one contiguous run and the heads are the distinct touched rows, in
+// key order; KEEP -- an entry of the range that does not match (what a delete leaves behind).
+constexpr int LIST_MATCH = 0, LIST_HEAD = 1, LIST_KEEP = 2;
+
+// is the matching entry e = T[i] a head; prev = T[i-1] when the caller holds it (have_prev)
+__device__ inline bool list_head(const LQuery& Q, const uint2* __restrict__ T, uint64_t i, uint2 e, bool m,
+                                 bool have_prev, uint2 prev) {
+    if (!m) return false;
+    if (i == Q.lo) return true;
+    const uint2 pv = have_prev ? prev : T[i - 1];
+    // the same row passes the same key predicates: only the subject word can differ
+    return pv.x != e.x || (Q.subj != ANY && pv.y != Q.subj);
+}
+
+// HEADS: the delete scan's form -- also counts the heads (hcnt, hwcnt) and flags any poisoned tuple
+// among the tuples matching the key part, subject filter or not (it is a match, or may be one)
+template <bool HEADS>
+__device__ __forceinline__ void list_count_body(const uint2* __restrict__ T, const uint2* __restrict__ keys,
+                                                const LQuery* __restrict__ qs, const LItem* __restrict__ items,
+                                                uint32_t tile, uint32_t* __restrict__ cnt, uint32_t* __restrict__ wcnt,
+                                                uint32_t* __restrict__ qpoison, uint32_t* __restrict__ hcnt,
+                                                uint32_t* __restrict__ hwcnt, uint32_t* wsum, uint32_t* wpoi,
+                                                uint32_t* whead) {
     const LItem it = items[blockIdx.x];
     const LQuery Q = qs[it.q];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quarter = tile / LIST_WAVES;
     const uint64_t ia = Q.lo + (uint64_t)it.tile * tile, ib = min(ia + tile, Q.hi);
     const uint64_t ws = min(ia + (uint64_t)wave * quarter, ib), we = min(ws + quarter, ib);
-    uint32_t c = 0;
+    uint32_t c = 0, hc = 0;
     bool anyp = false;
     for (uint64_t p0 = ws & ~1ull; p0 < we; p0 += 128) {
         uint2 a, b;
         bool m0, m1, p;
         list_pair(T, keys, Q, p0, lane, ws, we, a, b, m0, m1, p);
         c += __popcll(__ballot(m0)) + __popcll(__ballot(m1));
+        if constexpr (HEADS) {
+            const uint64_t e0 = p0 + 2ull * lane;
+            const bool h0 = list_head(Q, T, e0, a, m0, false, a), h1 = list_head(Q, T, e0 + 1, b, m1, true, a);
+            hc += __popcll(__ballot(h0)) + __popcll(__ballot(h1));
+        }
         const uint64_t bp = __ballot(p);
         anyp = anyp || bp != 0ull;
     }
     if (lane == 0) {
         wsum[wave] = c;
         wpoi[wave] = anyp ? 1u : 0u;
+        if constexpr (HEADS) whead[wave] = hc;
     }
     __syncthreads();
-    if (threadIdx.x < LIST_WAVES) wcnt[(uint64_t)blockIdx.x * LIST_WAVES + threadIdx.x] = wsum[threadIdx.x];
+    if (threadIdx.x < LIST_WAVES) {
+        wcnt[(uint64_t)blockIdx.x * LIST_WAVES + threadIdx.x] = wsum[threadIdx.x];
+        if constexpr (HEADS) hwcnt[(uint64_t)blockIdx.x * LIST_WAVES + threadIdx.x] = whead[threadIdx.x];
+    }
     if (threadIdx.x == 0) {
         uint32_t s = 0, p = 0;
         for (uint32_t w = 0; w < LIST_WAVES; ++w) {
@@ -166,10 +206,37 @@ list_count(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQ
             p |= wpoi[w];
         }
         cnt[blockIdx.x] = s;
-        // only a subject-filtered query reads it: a poisoned tuple among the tuples matching its
-        // namespace, object and relation may be a match the snapshot cannot see
-        if (p && Q.subj != ANY) atomicOr(qpoison + it.q, 1u);
+        if constexpr (HEADS) {
+            uint32_t h = 0;
+            for (uint32_t w = 0; w < LIST_WAVES; ++w) h += whead[w];
+            hcnt[blockIdx.x] = h;
+            if (p) atomicOr(qpoison + it.q, 1u);
+        } else {
+            // only a subject-filtered query reads it: a poisoned tuple among the tuples matching its
+            // namespace, object and relation may be a match the snapshot cannot see
+            if (p && Q.subj != ANY) atomicOr(qpoison + it.q, 1u);
+        }
     }
+}
+
+__global__ void __launch_bounds__(LIST_THREADS)
+list_count(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,
+           const LItem* __restrict__ items, uint32_t tile, uint32_t* __restrict__ cnt, uint32_t* __restrict__ wcnt,
+           uint32_t* __restrict__ qpoison) {
+    __shared__ uint32_t wsum[LIST_WAVES];
+    __shared__ uint32_t wpoi[LIST_WAVES];
+    list_count_body<false>(T, keys, qs, items, tile, cnt, wcnt, qpoison, nullptr, nullptr, wsum, wpoi, nullptr);
+}
+
+__global__ void __launch_bounds__(LIST_THREADS)
+list_count_heads(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,
+                 const LItem* __restrict__ items, uint32_t tile, uint32_t* __restrict__ cnt,
+                 uint32_t* __restrict__ wcnt, uint32_t* __restrict__ qpoison, uint32_t* __restrict__ hcnt,
+                 uint32_t* __restrict__ hwcnt) {
+    __shared__ uint32_t wsum[LIST_WAVES];
+    __shared__ uint32_t wpoi[LIST_WAVES];
+    __shared__ uint32_t whead[LIST_WAVES];
+    list_count_body<true>(T, keys, qs, items, tile, cnt, wcnt, qpoison, hcnt, hwcnt, wsum, wpoi, whead);
 }
 
 // totals of the group's queries [g0, g0 + nq): the distance between their first items' bases
@@ -179,44 +246,91 @@ __global__ void __launch_bounds__(256) list_totals(const uint64_t* __restrict__ 
     if (i < nq) tot[g0 + i] = base[ioff[i + 1]] - base[ioff[i]];
 }
 
-__global__ void __launch_bounds__(LIST_THREADS)
-list_emit(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,
-          const LItem* __restrict__ items, uint32_t tile, const uint32_t* __restrict__ cnt,
-          const uint32_t* __restrict__ wcnt, const uint64_t* __restrict__ base, const uint32_t* __restrict__ ioff,
-          uint32_t g0, const LWindow* __restrict__ wins, uint2* __restrict__ out, uint64_t out_n,
-          uint32_t* __restrict__ qpage_poison) {
+// MATCH: the list page (above).  HEAD: cnt / wcnt / base are the head counts; the heads' row ids go to
+// out, read as uint32_t[].  KEEP: cnt / wcnt / base are the match counts; entry e of [lo, hi) that does
+// not match goes to out[W.off + (e - lo) - (matches before e)]: the range with its matches squeezed out.
+template <int MODE>
+__device__ __forceinline__ void list_emit_body(const uint2* __restrict__ T, const uint2* __restrict__ keys,
+                                               const LQuery* __restrict__ qs, const LItem* __restrict__ items,
+                                               uint32_t tile, const uint32_t* __restrict__ cnt,
+                                               const uint32_t* __restrict__ wcnt, const uint64_t* __restrict__ base,
+                                               const uint32_t* __restrict__ ioff, uint32_t g0,
+                                               const LWindow* __restrict__ wins, uint2* __restrict__ out, uint64_t out_n,
+                                               uint32_t* __restrict__ qpage_poison) {
     const LItem it = items[blockIdx.x];
     const LWindow W = wins[it.q];
     if (W.whi <= W.wlo) return;
     const uint64_t r0 = base[blockIdx.x] - base[ioff[it.q - g0]];        // rank of the item's first match
-    if (r0 + cnt[blockIdx.x] <= W.wlo || r0 >= W.whi) return;
+    if constexpr (MODE != LIST_KEEP)
+        if (r0 + cnt[blockIdx.x] <= W.wlo || r0 >= W.whi) return;
     const LQuery Q = qs[it.q];
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, quarter = tile / LIST_WAVES;
     const uint64_t ia = Q.lo + (uint64_t)it.tile * tile, ib = min(ia + tile, Q.hi);
     const uint64_t ws = min(ia + (uint64_t)wave * quarter, ib), we = min(ws + quarter, ib);
     uint64_t r = r0;
     for (uint32_t w = 0; w < wave; ++w) r += wcnt[(uint64_t)blockIdx.x * LIST_WAVES + w];
-    if (r + wcnt[(uint64_t)blockIdx.x * LIST_WAVES + wave] <= W.wlo) return;    // the wave's matches miss the window
+    if constexpr (MODE != LIST_KEEP)
+        if (r + wcnt[(uint64_t)blockIdx.x * LIST_WAVES + wave] <= W.wlo) return;    // the wave's matches miss the window
     const uint64_t below = (1ull << lane) - 1ull;
-    for (uint64_t p0 = ws & ~1ull; p0 < we && r < W.whi; p0 += 128) {
+    for (uint64_t p0 = ws & ~1ull; p0 < we && (MODE == LIST_KEEP || r < W.whi); p0 += 128) {
         uint2 a, b;
         bool m0, m1, p;
         list_pair(T, keys, Q, p0, lane, ws, we, a, b, m0, m1, p);
+        if constexpr (MODE == LIST_HEAD) {
+            const uint64_t e0 = p0 + 2ull * lane;
+            const bool h0 = list_head(Q, T, e0, a, m0, false, a), h1 = list_head(Q, T, e0 + 1, b, m1, true, a);
+            m0 = h0;
+            m1 = h1;
+        }
         const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
         const uint64_t k0 = r + __popcll(b0 & below) + __popcll(b1 & below), k1 = k0 + (m0 ? 1u : 0u);
-        if (m0 && k0 >= W.wlo && k0 < W.whi) {
-            const uint64_t at = W.off + (k0 - W.wlo);
-            if (at < out_n) out[at] = a;
-            if (a.y == EDGE_POISON) atomicOr(qpage_poison + it.q, 1u);
-        }
-        if (m1 && k1 >= W.wlo && k1 < W.whi) {
-            const uint64_t at = W.off + (k1 - W.wlo);
-            if (at < out_n) out[at] = b;
-            if (b.y == EDGE_POISON) atomicOr(qpage_poison + it.q, 1u);
+        if constexpr (MODE == LIST_KEEP) {
+            const uint64_t e0 = p0 + 2ull * lane;
+            if (!m0 && e0 >= ws && e0 < we) {
+                const uint64_t at = W.off + (e0 - Q.lo) - k0;
+                if (at < out_n) out[at] = a;
+            }
+            if (!m1 && e0 + 1 >= ws && e0 + 1 < we) {
+                const uint64_t at = W.off + (e0 + 1 - Q.lo) - k1;
+                if (at < out_n) out[at] = b;
+            }
+        } else {
+            if (m0 && k0 >= W.wlo && k0 < W.whi) {
+                const uint64_t at = W.off + (k0 - W.wlo);
+                if constexpr (MODE == LIST_HEAD) {
+                    if (at < out_n) reinterpret_cast<uint32_t*>(out)[at] = a.x;
+                } else {
+                    if (at < out_n) out[at] = a;
+                    if (a.y == EDGE_POISON) atomicOr(qpage_poison + it.q, 1u);
+                }
+            }
+            if (m1 && k1 >= W.wlo && k1 < W.whi) {
+                const uint64_t at = W.off + (k1 - W.wlo);
+                if constexpr (MODE == LIST_HEAD) {
+                    if (at < out_n) reinterpret_cast<uint32_t*>(out)[at] = b.x;
+                } else {
+                    if (at < out_n) out[at] = b;
+                    if (b.y == EDGE_POISON) atomicOr(qpage_poison + it.q, 1u);
+                }
+            }
         }
         r += __popcll(b0) + __popcll(b1);
     }
 }
+
+#define LIST_EMIT_KERNEL(NAME, MODE)                                                                                  \
+    __global__ void __launch_bounds__(LIST_THREADS)                                                                   \
+    NAME(const uint2* __restrict__ T, const uint2* __restrict__ keys, const LQuery* __restrict__ qs,                  \
+         const LItem* __restrict__ items, uint32_t tile, const uint32_t* __restrict__ cnt,                            \
+         const uint32_t* __restrict__ wcnt, const uint64_t* __restrict__ base, const uint32_t* __restrict__ ioff,     \
+         uint32_t g0, const LWindow* __restrict__ wins, uint2* __restrict__ out, uint64_t out_n,                      \
+         uint32_t* __restrict__ qpage_poison) {                                                                       \
+        list_emit_body<MODE>(T, keys, qs, items, tile, cnt, wcnt, base, ioff, g0, wins, out, out_n, qpage_poison);    \
+    }
+LIST_EMIT_KERNEL(list_emit, LIST_MATCH)
+LIST_EMIT_KERNEL(list_emit_heads, LIST_HEAD)
+LIST_EMIT_KERNEL(list_emit_keep, LIST_KEEP)
+#undef LIST_EMIT_KERNEL
 
 uint32_t list_tile() {
     const char* e = getenv("KETO_LIST_TILE");
@@ -244,6 +358,7 @@ struct ListState {
     float build_ms = 0;
     hipStream_t stream = nullptr;
     LBuf qs, items, ioff, cnt, wcnt, base, tot, qpoison, qpage, wins, out, tmp;
+    LBuf hcnt, hwcnt, hbase;         // the delete scan's head counts (keto_snapshot_delete_query)
     void free_index() {
         if (T) (void)hipFree(T);
         if (keys) (void)hipFree(keys);
@@ -268,14 +383,23 @@ uint64_t list_device_bytes(ListCache& C) {
 
 namespace {
 
+void host_tables(const Snapshot& S, ListState& L);
+
 // the caller holds C.mu and S.rw shared
 ListState& host_index(const Snapshot& S, ListCache& C) {
     if (!C.state) C.state.reset(new ListState);
     ListState& L = *C.state;
     const uint64_t ver = S.version.load();
     if (L.host_built && L.version == ver) return L;
-    L.host_built = false;
     L.dev_built = false;                       // the device tables follow on the next list_batch
+    host_tables(S, L);
+    return L;
+}
+
+// ord and first of the snapshot as it stands, stamped with its version
+void host_tables(const Snapshot& S, ListState& L) {
+    const uint64_t ver = S.version.load();
+    L.host_built = false;
     L.ord = S.rows_in_key_order(RowKey{ANY_NS, ANY, ANY});
     const uint64_t m = L.ord.size();
     L.first.assign(m + 1, 0);
@@ -286,7 +410,6 @@ ListState& host_index(const Snapshot& S, ListCache& C) {
     for (uint64_t i = 0; i < m; ++i) L.first[i + 1] += L.first[i];
     L.version = ver;
     L.host_built = true;
-    return L;
 }
 
 // T and keys of the current host index, filled on host threads into pinned staging and uploaded
@@ -344,6 +467,7 @@ struct Plan {
     LQuery q{0, 0, ANY, ANY, ANY, 0};
     int64_t ns = ANY_NS;
     uint8_t status = KETO_LIST_OK;
+    uint64_t p0 = 0, p1 = 0;         // the rows ord[p0, p1) the range is made of
 };
 
 // whereQuery + whereSubject against the host tables: statuses, the entry range and the predicates
@@ -433,7 +557,9 @@ Plan resolve_list(const Snapshot& S, const ListState& L, const keto_list_req& rq
     }
     P.q.lo = L.first[p0];
     P.q.hi = L.first[p1];
-    if (P.q.lo == P.q.hi) P.q.lo = P.q.hi = 0, P.q.obj = P.q.rel = ANY;
+    P.p0 = p0;
+    P.p1 = p1;
+    if (P.q.lo == P.q.hi) P.q.lo = P.q.hi = 0, P.q.obj = P.q.rel = ANY, P.p0 = P.p1 = 0;
     return P;
 }
 
@@ -633,6 +759,284 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
     out.offsets[n] = w;
     out.tuples = tup;
     block.p = nullptr;
+}
+
+// ---- keto_snapshot_delete_query: the rows a query touches, and the index after the delete
+namespace {
+
+struct Widen {
+    __host__ __device__ uint64_t operator()(uint32_t c) const { return c; }
+};
+
+// items of the one query Q (entries [lo, hi) in tiles) and the exclusive sum of their counts
+struct OneQuery {
+    uint32_t m = 0;
+    LQuery* d_qs = nullptr;
+    LItem* d_items = nullptr;
+    uint32_t* d_ioff = nullptr;
+};
+
+OneQuery one_query(ListState& L, const LQuery& Q, uint32_t tile, std::vector<LItem>& items, uint32_t (&ioff)[2]) {
+    const uint64_t k = (Q.hi - Q.lo + tile - 1) / tile;
+    if (k > 0xFFFFFFF0ull) throw Error{KETO_E_RANGE, "keto_snapshot_delete_query: the query spans more than 2^32 tiles"};
+    OneQuery o;
+    o.m = (uint32_t)k;
+    items.resize(o.m);
+    for (uint32_t t = 0; t < o.m; ++t) items[t] = LItem{0, t};
+    ioff[0] = 0;
+    ioff[1] = o.m;
+    o.d_qs = L.qs.get<LQuery>(1);
+    o.d_items = L.items.get<LItem>(o.m);
+    o.d_ioff = L.ioff.get<uint32_t>(2);
+    HIP_OK(hipMemcpyAsync(o.d_qs, &Q, sizeof(LQuery), hipMemcpyHostToDevice, L.stream));
+    HIP_OK(hipMemcpyAsync(o.d_items, items.data(), (uint64_t)o.m * sizeof(LItem), hipMemcpyHostToDevice, L.stream));
+    HIP_OK(hipMemcpyAsync(o.d_ioff, ioff, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, L.stream));
+    return o;
+}
+
+void scan_counts(ListState& L, const uint32_t* d_cnt, uint64_t* d_base, uint32_t m) {
+    hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> cit(d_cnt, Widen{});
+    size_t tb = 0;
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cit, d_base, (uint64_t)m + 1, L.stream));
+    void* tmp = L.tmp.get<uint8_t>(tb);
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cit, d_base, (uint64_t)m + 1, L.stream));
+}
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() {
+        HIP_OK(hipEventCreate(&a));
+        if (hipEventCreate(&b) != hipSuccess) {
+            (void)hipEventDestroy(a);
+            throw Error{KETO_E_HIP, "hipEventCreate"};
+        }
+    }
+    ~EventPair() {
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+    }
+};
+
+// the device pass: one count launch (matches, heads, the poison flag), the scans, one host sync, then
+// the HEAD emit of the touched row ids into a pinned block sized exactly.  The caller holds C.mu.
+void scan_device(ListState& L, const LQuery& Q, uint64_t max_rows, DeleteScan& out) {
+    const uint32_t tile = list_tile();
+    hipStream_t st = L.stream;
+    EventPair ev;
+    HIP_OK(hipEventRecord(ev.a, st));
+    std::vector<LItem> items;
+    uint32_t ioff[2];
+    uint64_t tot[2] = {0, 0};
+    uint32_t poison = 0;
+    const OneQuery o = one_query(L, Q, tile, items, ioff);
+    const uint32_t m = o.m;
+    if (m) {
+        uint32_t* d_cnt = L.cnt.get<uint32_t>((uint64_t)m + 1);
+        uint32_t* d_wcnt = L.wcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
+        uint64_t* d_base = L.base.get<uint64_t>((uint64_t)m + 1);
+        uint32_t* d_hcnt = L.hcnt.get<uint32_t>((uint64_t)m + 1);
+        uint32_t* d_hwcnt = L.hwcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
+        uint64_t* d_hbase = L.hbase.get<uint64_t>((uint64_t)m + 1);
+        uint32_t* d_qpoison = L.qpoison.get<uint32_t>(1);
+        HIP_OK(hipMemsetAsync(d_cnt + m, 0, sizeof(uint32_t), st));
+        HIP_OK(hipMemsetAsync(d_hcnt + m, 0, sizeof(uint32_t), st));
+        HIP_OK(hipMemsetAsync(d_qpoison, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(list_count_heads, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, o.d_qs, o.d_items, tile, d_cnt,
+                           d_wcnt, d_qpoison, d_hcnt, d_hwcnt);
+        HIP_OK(hipGetLastError());
+        scan_counts(L, d_cnt, d_base, m);
+        scan_counts(L, d_hcnt, d_hbase, m);
+        HIP_OK(hipMemcpyAsync(&tot[0], d_base + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&tot[1], d_hbase + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(&poison, d_qpoison, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));                 // the one host sync: totals -> the block's size
+    }
+    out.matches = tot[0];
+    out.heads = tot[1];
+    out.poisoned = poison != 0;
+    if (m && out.heads && !out.poisoned && out.heads <= max_rows) {
+        const LWindow win{0, out.heads, 0};
+        LWindow* d_wins = L.wins.get<LWindow>(1);
+        uint32_t* d_out = L.out.get<uint32_t>(out.heads);
+        HIP_OK(hipMemcpyAsync(d_wins, &win, sizeof(LWindow), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(list_emit_heads, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, o.d_qs, (const LItem*)o.d_items,
+                           tile, (const uint32_t*)L.hcnt.p, (const uint32_t*)L.hwcnt.p, (const uint64_t*)L.hbase.p,
+                           (const uint32_t*)o.d_ioff, 0u, d_wins, reinterpret_cast<uint2*>(d_out), out.heads, nullptr);
+        HIP_OK(hipGetLastError());
+        struct Block {
+            void* p;
+            ~Block() { pinned_give(p); }
+        } block{pinned_take(out.heads * sizeof(uint32_t))};
+        HIP_OK(hipMemcpyAsync(block.p, d_out, out.heads * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        const uint32_t* r = static_cast<const uint32_t*>(block.p);
+        out.rows.assign(r, r + out.heads);
+    }
+    HIP_OK(hipEventRecord(ev.b, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipEventElapsedTime(&out.scan_ms, ev.a, ev.b));
+}
+
+// the host pass over the candidate rows ord[p0, p1): key predicates per row, the subject word by a
+// scan of the row's edges
+void scan_host(const Snapshot& S, const ListState& L, const Plan& P, DeleteScan& out) {
+    const uint64_t n = P.p1 - P.p0;
+    const unsigned th = (P.q.hi - P.q.lo) >= par_min() ? build_threads() : 1u;
+    struct Part {
+        std::vector<uint32_t> rows;
+        uint64_t matches = 0;
+        bool poisoned = false;
+    };
+    std::vector<Part> parts(std::max(1u, th));
+    par_chunks(n, th, 1 << 12, [&](uint64_t b, uint64_t e, unsigned t) {
+        Part& p = parts[t];
+        for (uint64_t i = P.p0 + b; i < P.p0 + e; ++i) {
+            const uint32_t row = L.ord[i];
+            const RowKey& k = S.row_key[row];
+            if ((P.q.obj != ANY && k.obj != P.q.obj) || (P.q.rel != ANY && k.rel != P.q.rel)) continue;
+            const auto ed = S.row_edges(row);
+            if (S.row_pp[row] != NO_PAGE && std::find(ed.first, ed.first + ed.second, EDGE_POISON) != ed.first + ed.second)
+                p.poisoned = true;
+            const uint64_t c = P.q.subj == ANY ? ed.second : (uint64_t)std::count(ed.first, ed.first + ed.second, P.q.subj);
+            if (!c) continue;
+            p.matches += c;
+            p.rows.push_back(row);
+        }
+    });
+    for (Part& p : parts) {
+        out.matches += p.matches;
+        out.poisoned = out.poisoned || p.poisoned;
+        out.rows.insert(out.rows.end(), p.rows.begin(), p.rows.end());
+    }
+    out.heads = out.rows.size();
+}
+
+}  // namespace
+
+void delete_scan(const Snapshot& S, ListCache& C, const keto_list_req& rq, uint64_t max_rows, DeleteScan& out) {
+    out = DeleteScan{};
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool keyed = rq.namespace_.n && rq.object.n && rq.relation.n;      // one row: always the host's
+    std::unique_lock<std::mutex> lk(C.mu);
+    const ListState& L = host_index(S, C);
+    const Plan P = resolve_list(S, L, rq);
+    if (P.status != KETO_LIST_OK) {
+        // GetNamespaceByName fails the reference's transaction (relationtuples.go:161,180)
+        std::string_view name = sv(rq.namespace_);
+        if (name.empty() || S.ns_index(name) >= 0) name = sv(rq.subject.set_namespace);
+        throw Error{KETO_E_INVALID, "Unknown namespace with name " + std::string(name) + "."};
+    }
+    out.subject = P.q.subj;
+    out.lo = P.q.lo;
+    out.hi = P.q.hi;
+    out.obj = P.q.obj;
+    out.rel = P.q.rel;
+    out.version = L.version;
+    if (P.q.lo == P.q.hi) {                               // nothing can match
+        out.scan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return;
+    }
+    if (!keyed && S.dev && S.n_parts == 1 && L.dev_built && L.device >= 0) {
+        out.path = KETO_DELETE_PATH_DEVICE;
+        HIP_OK(hipSetDevice(L.device));
+        scan_device(*C.state, P.q, max_rows, out);
+    } else {
+        // the host tables of this version stay as they are while the caller holds the lock shared:
+        // list calls go on during the scan
+        lk.unlock();
+        scan_host(S, L, P, out);
+        out.scan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (out.heads > max_rows) out.rows.clear();
+    std::sort(out.rows.begin(), out.rows.end());
+    out.rows.erase(std::unique(out.rows.begin(), out.rows.end()), out.rows.end());
+}
+
+namespace {
+
+// the new T: entries [0, lo), the kept entries of [lo, hi), entries [hi, N) behind them
+void patch_device(ListState& L, const DeleteScan& sc, uint64_t N) {
+    const uint32_t tile = list_tile();
+    hipStream_t st = L.stream;
+    const uint64_t newN = N - sc.matches, t_entries = (newN + 2) & ~1ull, old_entries = (N + 2) & ~1ull;
+    struct Fresh {
+        uint2* p = nullptr;
+        ~Fresh() {
+            if (p) (void)hipFree(p);
+        }
+    } fresh;
+    HIP_OK(hipMalloc((void**)&fresh.p, t_entries * sizeof(uint2)));
+    HIP_OK(hipMemsetAsync(fresh.p + newN, 0, (t_entries - newN) * sizeof(uint2), st));
+    if (sc.lo) HIP_OK(hipMemcpyAsync(fresh.p, L.T, sc.lo * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+    const LQuery Q{sc.lo, sc.hi, sc.obj, sc.rel, sc.subject, 0};
+    std::vector<LItem> items;
+    uint32_t ioff[2];
+    const OneQuery o = one_query(L, Q, tile, items, ioff);
+    const uint32_t m = o.m;
+    uint32_t* d_cnt = L.cnt.get<uint32_t>((uint64_t)m + 1);
+    uint32_t* d_wcnt = L.wcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
+    uint64_t* d_base = L.base.get<uint64_t>((uint64_t)m + 1);
+    uint32_t* d_qpoison = L.qpoison.get<uint32_t>(1);
+    HIP_OK(hipMemsetAsync(d_cnt + m, 0, sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(d_qpoison, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(list_count, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, o.d_qs, o.d_items, tile, d_cnt, d_wcnt,
+                       d_qpoison);
+    HIP_OK(hipGetLastError());
+    scan_counts(L, d_cnt, d_base, m);
+    uint64_t total = 0;
+    HIP_OK(hipMemcpyAsync(&total, d_base + m, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (total != sc.matches) throw Error{KETO_E_INVALID, "the list index does not hold the deleted tuples"};
+    const LWindow win{0, sc.hi - sc.lo, sc.lo};
+    LWindow* d_wins = L.wins.get<LWindow>(1);
+    HIP_OK(hipMemcpyAsync(d_wins, &win, sizeof(LWindow), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(list_emit_keep, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, o.d_qs, (const LItem*)o.d_items, tile,
+                       (const uint32_t*)d_cnt, (const uint32_t*)d_wcnt, (const uint64_t*)d_base, (const uint32_t*)o.d_ioff, 0u,
+                       d_wins, fresh.p, sc.hi - sc.matches, nullptr);
+    HIP_OK(hipGetLastError());
+    if (N > sc.hi)
+        HIP_OK(hipMemcpyAsync(fresh.p + (sc.hi - sc.matches), L.T + sc.hi, (N - sc.hi) * sizeof(uint2), hipMemcpyDeviceToDevice,
+                              st));
+    HIP_OK(hipStreamSynchronize(st));
+    std::swap(L.T, fresh.p);                              // the old T is freed with `fresh`
+    L.bytes = L.bytes - old_entries * sizeof(uint2) + t_entries * sizeof(uint2);
+}
+
+}  // namespace
+
+bool delete_index_patch(const Snapshot& S, ListCache& C, const DeleteScan& sc) noexcept {
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.state) return false;
+    ListState& L = *C.state;
+    try {
+        // a list call may have built the device half between the scan and the commit: it is of the
+        // scanned version all the same (writes are one at a time)
+        bool dev = L.dev_built && L.host_built && L.version == sc.version && S.dev && S.n_parts == 1;
+        if (dev && sc.matches) {
+            HIP_OK(hipSetDevice(L.device));
+            patch_device(L, sc, L.first.back());
+        }
+        if (!dev) {
+            // no device half to keep: the host half is rebuilt by the next list call, under the shared
+            // lock, instead of here under the exclusive one
+            L.host_built = false;
+            if (L.device >= 0) {
+                (void)hipSetDevice(L.device);
+                L.free_index();
+            }
+            return false;
+        }
+        host_tables(S, L);
+        L.dev_built = true;
+        return true;
+    } catch (...) {
+        L.host_built = false;
+        if (L.device >= 0) {
+            (void)hipSetDevice(L.device);
+            L.free_index();
+        }
+        return false;
+    }
 }
 
 }  // namespace keto

@@ -35,4 +35,30 @@ void list_plan(const Snapshot& s, ListCache& c, const keto_list_req* reqs, uint3
 void list_batch(Snapshot& s, ListCache& c, const keto_list_req* reqs, uint32_t n, ListResult& out);
 uint64_t list_device_bytes(ListCache& c);   // device memory of the list index (0 before the first list_batch)
 
+// keto_snapshot_delete_query: the rows a whereQuery / whereSubject touches (list.hip)
+struct DeleteScan {
+    std::vector<uint32_t> rows;      // the tuple rows that lose a tuple, ascending and distinct
+    uint32_t subject = ANY;          // the subject word that leaves them (ANY: every tuple of the row)
+    uint64_t matches = 0;            // tuples matched (SQL: rows affected)
+    uint64_t heads = 0;              // rows touched; rows is left empty when there are more than max_rows
+    bool poisoned = false;           // a poisoned tuple among the tuples matching the key part
+    uint32_t path = KETO_DELETE_PATH_HOST;
+    float scan_ms = 0;
+    // the query as the scan ran it on the list index of `version`: entries [lo, hi) and the key
+    // predicates left over -- what delete_index_patch squeezes the matches out of
+    uint64_t lo = 0, hi = 0, version = 0;
+    uint32_t obj = ANY, rel = ANY;
+};
+// The caller holds the snapshot's lock shared (and not c.mu, which the scan takes and releases).  Throws
+// KETO_E_INVALID for an unknown namespace.  The device pass runs when the snapshot is on a device,
+// unpartitioned, its device list index is current and the query is not fully keyed; no index is built.
+void delete_scan(const Snapshot& s, ListCache& c, const keto_list_req& q, uint64_t max_rows, DeleteScan& out);
+// After the commit, the caller holding the snapshot's lock exclusive: patches the device list index
+// that was current at scan.version (out of place: [0, lo), the kept entries of [lo, hi), [hi, N)) and
+// rebuilds the host half, both stamped with the new version.  Returns true when the device index is
+// current afterwards; any failure drops the index (the next list call rebuilds it) and returns false.
+// Without a device index to keep, the host half is only marked stale (the next list call rebuilds it
+// under the shared lock).
+bool delete_index_patch(const Snapshot& s, ListCache& c, const DeleteScan& scan) noexcept;
+
 }  // namespace keto
