@@ -652,8 +652,8 @@ const uint8_t* keto_encoded_status(const keto_encoded* e);             /* n x KE
  *
  * The first list call on a snapshot version builds the list index on host threads and uploads it
  * (8 B per tuple plus 8 B per row of device memory, counted in keto_snapshot_stats.device_bytes); a
- * keto_snapshot_apply invalidates it and the next list call rebuilds all of it; a
- * keto_snapshot_delete_query patches it to the new version (below).
+ * keto_snapshot_apply leaves it stale and the next list call patches it, or rebuilds all of it
+ * (keto_list_index_info, below); a keto_snapshot_delete_query patches it to the new version (below).
  * Errors: a host-only snapshot is KETO_E_HIP, any part of a partitioned upload (n_parts > 1)
  * KETO_E_INVALID; n = 0 gives count 0 and offsets {0}.  Calls take the snapshot's lock shared, as
  * keto_expand_batch does, and run one at a time per snapshot. */
@@ -692,6 +692,35 @@ int keto_listed_timing(const keto_listed*, float* index_ms, float* scan_ms);
  * compares it); status = KETO_LIST_OK or KETO_LIST_NOT_FOUND (unknown namespace). */
 typedef struct { uint64_t lo, hi; int64_t ns; uint32_t obj, rel, subject; uint8_t status; } keto_list_plan_t;
 int keto_list_plan(const keto_snapshot* s, const keto_list_req* reqs, uint32_t n, keto_list_plan_t* out);
+
+/* The list index across writes (repo:keto_amd/csrc/list.hip).  keto_snapshot_apply leaves the index as
+ * it is and only notes the ids of the rows it changed in a journal (a deduplicated set, relative to the
+ * version the index describes).  The first list call after one or more writes patches the index from
+ * the journal instead of rebuilding it: the host half (the rows in key order and their first entries)
+ * by a merge, the device half by a splice -- a new T is written out of place from the old one and the
+ * changed rows' new entries (old and new T live together until the splice is done); keys[] takes the
+ * new rows' keys.  The next list call rebuilds everything, as before, when the journal holds more
+ * than KETO_LIST_PATCH_MAX_ROWS distinct rows (environment, default 2^12), with KETO_LIST_PATCH=0 in
+ * the environment, after a keto_snapshot_delete_query that found the index stale, or when any step of
+ * the device patch fails.  keto_list_plan and a delete's host scan patch the host half alone; the device
+ * half follows on the next keto_list_batch.
+ *
+ * keto_list_index_info reports that state; it builds nothing and works on any snapshot (all zeros
+ * before the first list, plan or delete call). */
+typedef struct {
+    uint32_t host_built, host_current;   /* ord/first exist; and are at the snapshot's version */
+    uint32_t dev_built, dev_current;     /* T/keys exist; and are at the snapshot's version */
+    uint64_t host_version, dev_version;  /* valid when built */
+    uint64_t entries;                    /* N of the device index (0 without one) */
+    uint64_t device_bytes;
+    uint32_t journal_valid;              /* 1 = the next list call can patch */
+    uint32_t journal_rows;               /* distinct rows noted since dev_version (host_version without a device half) */
+    uint64_t host_builds, host_patches;  /* since the handle was made */
+    uint64_t dev_builds, dev_patches;    /* delete_index_patch counts as a dev_patch */
+    uint64_t last_segments, last_staged_entries;   /* of the last device patch */
+    float    last_host_ms, last_device_ms;         /* last build or patch: host wall; HIP events around the splice (0 for a build) */
+} keto_list_index_info_t;
+int keto_list_index_info(const keto_snapshot* s, keto_list_index_info_t* out);
 
 /* ---- Delete by query: DeleteAllRelationTuples on a live snapshot (repo:keto_amd/csrc/list.hip, delta.cpp) ----
  * keto_snapshot_delete_query follows relationtuple.Manager.DeleteAllRelationTuples

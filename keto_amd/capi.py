@@ -46,7 +46,7 @@ EXPORTS = [
     "keto_encoded_bytes", "keto_encoded_offsets", "keto_encoded_status",
     "keto_list_batch", "keto_listed_free", "keto_listed_count", "keto_listed_tuples", "keto_listed_offsets",
     "keto_listed_status", "keto_listed_next_page", "keto_listed_totals", "keto_listed_timing", "keto_list_plan",
-    "keto_snapshot_delete_query",
+    "keto_snapshot_delete_query", "keto_list_index_info",
 ]
 DELETE_PATH_HOST, DELETE_PATH_DEVICE = 0, 1
 LIST_OK, LIST_NOT_FOUND, LIST_UNDECIDED = 0, 1, 2
@@ -143,6 +143,15 @@ class KListPlan(C.Structure):
 class KDeleteInfo(C.Structure):
     _fields_ = [("deleted", C.c_uint64), ("rows_touched", C.c_uint64), ("version", C.c_uint64), ("path", C.c_uint32),
                 ("index_kept", C.c_uint32), ("scan_ms", C.c_float), ("apply_ms", C.c_float)]
+
+
+class KListIndexInfo(C.Structure):
+    _fields_ = [("host_built", C.c_uint32), ("host_current", C.c_uint32), ("dev_built", C.c_uint32),
+                ("dev_current", C.c_uint32), ("host_version", C.c_uint64), ("dev_version", C.c_uint64),
+                ("entries", C.c_uint64), ("device_bytes", C.c_uint64), ("journal_valid", C.c_uint32),
+                ("journal_rows", C.c_uint32), ("host_builds", C.c_uint64), ("host_patches", C.c_uint64),
+                ("dev_builds", C.c_uint64), ("dev_patches", C.c_uint64), ("last_segments", C.c_uint64),
+                ("last_staged_entries", C.c_uint64), ("last_host_ms", C.c_float), ("last_device_ms", C.c_float)]
 
 
 LIST_TUPLE_DTYPE = np.dtype([("row", "<u4"), ("subject", "<u4")])
@@ -856,6 +865,14 @@ class Snapshot:
         opt = lambda v: None if v == 0xFFFFFFFF else int(v)
         return [{"lo": int(p.lo), "hi": int(p.hi), "ns": None if p.ns == -(1 << 63) else int(p.ns), "obj": opt(p.obj),
                  "rel": opt(p.rel), "subject": opt(p.subject), "status": int(p.status)} for p in out[:n]]
+
+    def list_index_info(self) -> dict:
+        """keto_list_index_info: the state of the list index -- which halves exist and are current, the
+        journal of written rows the next list call patches from, and the build / patch counters and
+        times.  Builds nothing; all zeros before the first list, plan or delete call."""
+        info = KListIndexInfo()
+        _check(self.lib.keto_list_index_info(self.h, C.byref(info)))
+        return {n: (float if t is C.c_float else int)(getattr(info, n)) for n, t in KListIndexInfo._fields_}
 
     def list_batch_raw(self, queries):
         """keto_list_batch -> (status[n], offsets[n+1], tuples (LIST_TUPLE_DTYPE), next_page[n], totals[n],

@@ -634,6 +634,7 @@ int keto_snapshot_apply(keto_snapshot* h, const keto_tuple* inserts, uint64_t n_
         } retire{S, xl};
         const auto t0 = std::chrono::steady_clock::now();
         auto t1 = t0;
+        const uint64_t ver0 = S.version;
         apply_writes(S, inserts, n_inserts, deletes, n_deletes, [&] {
             t1 = std::chrono::steady_clock::now();
             rl.unlock();
@@ -641,6 +642,9 @@ int keto_snapshot_apply(keto_snapshot* h, const keto_tuple* inserts, uint64_t n_
             xl.lock();
             lock_trace("apply: rw exclusive");
         });
+        // the list index stays as it is: the next list call patches it from the rows noted here
+        // (a refused write threw above, the snapshot unchanged)
+        if (S.version != ver0) list_note_rows(h->list, S.dirty.data(), S.dirty.size(), ver0, S.version);
         const auto t2 = std::chrono::steady_clock::now();
         device_apply(S);
         lock_trace("apply: device_apply done");
@@ -1390,6 +1394,15 @@ int keto_listed_timing(const keto_listed* l, float* index_ms, float* scan_ms) {
         if (!l) throw Error{KETO_E_INVALID, "NULL argument"};
         if (index_ms) *index_ms = l->r.index_ms;
         if (scan_ms) *scan_ms = l->r.scan_ms;
+        return KETO_OK;
+    });
+}
+
+int keto_list_index_info(const keto_snapshot* h, keto_list_index_info_t* out) {
+    return guarded([&] {
+        if (!h || !out) throw Error{KETO_E_INVALID, "NULL argument"};
+        std::shared_lock<RwGate> lk(h->s->rw);
+        list_index_info(*h->s, h->list, out);
         return KETO_OK;
     });
 }

@@ -30,8 +30,14 @@
 // No atomic decides an order: the only atomics OR a per-query poison flag.  One host sync sits between
 // the passes (totals -> result sizes, statuses, tokens).
 //
-// Known limit: a write (keto_snapshot_apply) invalidates the whole index; the next list call
-// rebuilds and uploads all of it.
+// Across writes: keto_snapshot_apply leaves the index stale and notes the rows it changed in a journal
+// (list_note_rows).  The first list call after it patches the index: ord / first by a merge of the
+// journal's tuple rows (host_patch), T by a splice (device_patch: a segment per changed row, the new
+// entries staged and uploaded, list_splice writing a fresh T' from T and the staged block, the part in
+// front of the first segment a plain copy), keys[] by the appended rows' keys.  The host half may run
+// ahead of the device half (keto_list_plan, a delete's host scan); the journal is always relative to
+// the device half.  A journal past KETO_LIST_PATCH_MAX_ROWS rows, KETO_LIST_PATCH=0, a delete that found
+// the index stale or a failing patch mean a rebuild of everything, as on the first call.
 //
 // keto_snapshot_delete_query (DeleteAllRelationTuples, relationtuples.go:225-236) uses the same
 // resolver and, when the device index is current, the same passes to find the rows a query touches:
@@ -332,6 +338,77 @@ LIST_EMIT_KERNEL(list_emit_heads, LIST_HEAD)
 LIST_EMIT_KERNEL(list_emit_keep, LIST_KEEP)
 #undef LIST_EMIT_KERNEL
 
+// One changed tuple row of a splice: its entries [old_pos, old_pos + old_len) of T become
+// [new_pos, new_pos + new_len) of T', taken from the staged block at `staged`.  A new row has
+// old_len = 0 at its insertion point, a row that left the index new_len = 0.  Sorted by position (old
+// and new alike: the rows between two segments keep their entries and their order).
+struct LSeg {
+    uint64_t old_pos, old_len, new_pos, new_len, staged;
+};
+
+// T'[base, newN), base = the first segment's position: one block per tile of output entries.  Entry j
+// belongs to the last segment s whose new_pos is at or before it (of several segments at one position
+// only the last can have entries): inside s's new extent it is a staged entry, behind it the entry of
+// T as far behind s's old extent.  The block narrows the segments of its tile by two binary searches,
+// a lane searches only those; 8-B accesses, consecutive lanes on consecutive entries on both sides
+// (old and new positions differ by any count, odd ones included, so nothing wider is assumed).
+__global__ void __launch_bounds__(LIST_THREADS)
+list_splice(const uint2* __restrict__ T, uint64_t old_n, const LSeg* __restrict__ segs, uint32_t nseg,
+            const uint2* __restrict__ staged, uint64_t staged_n, uint64_t base, uint32_t tile, uint2* __restrict__ out,
+            uint64_t new_n) {
+    const uint64_t ja = base + (uint64_t)blockIdx.x * tile;
+    if (ja >= new_n || nseg == 0) return;
+    const uint64_t jb = min(ja + tile, new_n);
+    uint32_t lo = 0, hi = nseg;                             // segs[lo].new_pos <= ja: segs[0].new_pos == base
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (segs[mid].new_pos <= ja) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t s_lo = lo;
+    hi = nseg;                                              // the last segment starting inside the tile, or s_lo
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (segs[mid].new_pos < jb) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t s_hi = lo;
+    for (uint64_t j = ja + threadIdx.x; j < jb; j += LIST_THREADS) {
+        uint32_t a = s_lo, b = s_hi + 1;
+        while (b - a > 1) {
+            const uint32_t mid = a + (b - a) / 2;
+            if (segs[mid].new_pos <= j) a = mid;
+            else b = mid;
+        }
+        const LSeg g = segs[a];
+        const uint64_t ne = g.new_pos + g.new_len;
+        uint2 v = make_uint2(0, 0);
+        if (j < ne) {
+            const uint64_t at = g.staged + (j - g.new_pos);
+            if (at < staged_n) v = staged[at];
+        } else {
+            const uint64_t at = g.old_pos + g.old_len + (j - ne);
+            if (at < old_n) v = T[at];
+        }
+        out[j] = v;
+    }
+}
+
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() {
+        HIP_OK(hipEventCreate(&a));
+        if (hipEventCreate(&b) != hipSuccess) {
+            (void)hipEventDestroy(a);
+            throw Error{KETO_E_HIP, "hipEventCreate"};
+        }
+    }
+    ~EventPair() {
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+    }
+};
+
 uint32_t list_tile() {
     const char* e = getenv("KETO_LIST_TILE");
     if (!e) return 4096;
@@ -349,9 +426,11 @@ struct ListState {
     uint64_t version = ~0ull;
     std::vector<uint32_t> ord;
     std::vector<uint64_t> first;     // ord.size() + 1
-    // device part
+    // device part: T of dev_n entries and keys[] of keys_n rows (keys_cap allocated), of dev_version
     int device = -1;
     bool dev_built = false;
+    uint64_t dev_version = ~0ull;
+    uint64_t dev_n = 0, keys_n = 0, keys_cap = 0;
     uint2* T = nullptr;
     uint2* keys = nullptr;
     uint64_t bytes = 0;
@@ -359,12 +438,43 @@ struct ListState {
     hipStream_t stream = nullptr;
     LBuf qs, items, ioff, cnt, wcnt, base, tot, qpoison, qpage, wins, out, tmp;
     LBuf hcnt, hwcnt, hbase;         // the delete scan's head counts (keto_snapshot_delete_query)
+    LBuf segs, staged;               // the splice's segment table and new entries
+    // The device half may lag the host half (a keto_list_plan or a delete's host scan patched the host
+    // half first): then dev_ord / dev_first are the ord / first T was built from, moved here by that
+    // patch.  Otherwise ord / first describe T.
+    bool dev_desc = false;
+    std::vector<uint32_t> dev_ord;
+    std::vector<uint64_t> dev_first;
+    // The journal: rows written since dev_version (since `version` without a device half), complete up to
+    // the snapshot version j_upto.  Appended raw by writers, deduplicated by journal_settle; [0, j_mark)
+    // is sorted and distinct.
+    bool j_valid = false;
+    uint64_t j_upto = 0;
+    size_t j_mark = 0;
+    std::vector<uint32_t> journal;
+    // keto_list_index_info
+    uint64_t host_builds = 0, host_patches = 0, dev_builds = 0, dev_patches = 0;
+    uint64_t last_segments = 0, last_staged = 0;
+    float last_host_ms = 0, last_device_ms = 0;
     void free_index() {
         if (T) (void)hipFree(T);
         if (keys) (void)hipFree(keys);
         T = keys = nullptr;
         bytes = 0;
+        dev_n = keys_n = keys_cap = 0;
         dev_built = false;
+        drop_dev_desc();
+    }
+    void drop_dev_desc() {
+        dev_desc = false;
+        std::vector<uint32_t>().swap(dev_ord);
+        std::vector<uint64_t>().swap(dev_first);
+    }
+    void journal_reset(bool valid, uint64_t upto) {
+        j_valid = valid;
+        j_upto = upto;
+        j_mark = 0;
+        std::vector<uint32_t>().swap(journal);
     }
     ~ListState() {
         if (device < 0) return;
@@ -384,6 +494,35 @@ uint64_t list_device_bytes(ListCache& C) {
 namespace {
 
 void host_tables(const Snapshot& S, ListState& L);
+void host_patch(const Snapshot& S, ListState& L);
+
+bool patch_enabled() {
+    const char* e = getenv("KETO_LIST_PATCH");
+    return !e || atol(e) != 0;
+}
+
+// The most distinct rows a journal holds.  Measured on the 10M-tuple graph (4.3M rows,
+// profiles/config2_list_patch.log): a patch beats the rebuild 2x to 20x at 100 touched rows, is level
+// with it around 10,000 and loses 4x at 10^6; 2^12 stays on the winning side.
+uint64_t patch_max_rows() {
+    const char* e = getenv("KETO_LIST_PATCH_MAX_ROWS");
+    return e ? (uint64_t)std::max(0ll, atoll(e)) : 1ull << 12;
+}
+
+// the journal as a sorted set; past the row bound it marks itself invalid and frees its memory
+void journal_settle(ListState& L) {
+    if (!L.j_valid) return;
+    if (L.j_mark != L.journal.size()) {
+        std::sort(L.journal.begin(), L.journal.end());
+        L.journal.erase(std::unique(L.journal.begin(), L.journal.end()), L.journal.end());
+        L.j_mark = L.journal.size();
+    }
+    if (L.journal.size() > patch_max_rows()) L.journal_reset(false, 0);
+}
+
+float ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // the caller holds C.mu and S.rw shared
 ListState& host_index(const Snapshot& S, ListCache& C) {
@@ -391,15 +530,24 @@ ListState& host_index(const Snapshot& S, ListCache& C) {
     ListState& L = *C.state;
     const uint64_t ver = S.version.load();
     if (L.host_built && L.version == ver) return L;
-    L.dev_built = false;                       // the device tables follow on the next list_batch
-    host_tables(S, L);
+    const auto t0 = std::chrono::steady_clock::now();
+    journal_settle(L);
+    if (L.host_built && L.j_valid && L.j_upto == ver && patch_enabled()) {
+        host_patch(S, L);                      // the device half follows on the next list_batch, by a splice
+    } else {
+        L.dev_built = false;                   // the device tables follow on the next list_batch, rebuilt
+        L.drop_dev_desc();
+        host_tables(S, L);
+    }
+    L.last_host_ms = ms_since(t0);
     return L;
 }
 
-// ord and first of the snapshot as it stands, stamped with its version
+// ord and first of the snapshot as it stands, stamped with its version; the journal starts afresh
 void host_tables(const Snapshot& S, ListState& L) {
     const uint64_t ver = S.version.load();
     L.host_built = false;
+    L.journal_reset(false, 0);
     L.ord = S.rows_in_key_order(RowKey{ANY_NS, ANY, ANY});
     const uint64_t m = L.ord.size();
     L.first.assign(m + 1, 0);
@@ -410,6 +558,110 @@ void host_tables(const Snapshot& S, ListState& L) {
     for (uint64_t i = 0; i < m; ++i) L.first[i + 1] += L.first[i];
     L.version = ver;
     L.host_built = true;
+    L.host_builds += 1;
+    L.journal_reset(patch_enabled(), ver);
+}
+
+// is row r one that holds tuples (not a materialized wildcard row), and is it a member of ord now:
+// Snapshot::rows_in_key_order's rule
+inline bool tuple_row(const Snapshot& S, uint32_t r) {
+    if (r < S.n_real_rows) return true;
+    const RowKey& k = S.row_key[r];
+    return k.ns != ANY_NS && k.obj != ANY && k.rel != ANY;
+}
+inline bool in_ord(const Snapshot& S, uint32_t r) {
+    if (r < S.n_real_rows) return true;
+    auto it = S.row_over.find(r);
+    return it != S.row_over.end() && !it->second.empty();
+}
+
+// the journal's tuple rows in key order (the journal is settled: ascending row ids).  The build's real
+// rows are in key order by id; only rows added since need sorting, and one merge joins the two.
+std::vector<uint32_t> journal_tuple_rows(const Snapshot& S, const ListState& L) {
+    std::vector<uint32_t> real, extra;
+    real.reserve(L.journal.size());
+    for (uint32_t r : L.journal) {
+        if (r >= S.n_rows() || !tuple_row(S, r)) continue;
+        (r < S.n_real_rows ? real : extra).push_back(r);
+    }
+    if (extra.empty()) return real;
+    auto less = [&](uint32_t a, uint32_t b) { return S.key_cmp_bytes(S.row_key[a], S.row_key[b]) < 0; };
+    std::sort(extra.begin(), extra.end(), less);
+    std::vector<uint32_t> jr(real.size() + extra.size());
+    std::merge(real.begin(), real.end(), extra.begin(), extra.end(), jr.begin(), less);
+    return jr;
+}
+
+// Where row r is in ord[from, ...) or would be inserted (row keys never change and are distinct: a
+// search by key); found: ord holds it there.  The callers walk the journal in key order, so the place
+// is usually near `from`: the search gallops from there before it bisects.
+inline uint64_t ord_place(const Snapshot& S, const std::vector<uint32_t>& ord, uint64_t from, uint32_t r, bool& found) {
+    const RowKey& k = S.row_key[r];
+    auto before = [&](uint64_t i) { return S.key_cmp_bytes(S.row_key[ord[i]], k) < 0; };
+    const uint64_t m = ord.size();
+    uint64_t lo = from, hi = m;                             // ord[lo - 1] < k (or lo == from), ord[hi] >= k (or hi == m)
+    for (uint64_t step = 1; lo < m; step *= 2) {
+        const uint64_t probe = std::min(m - 1, lo + step - 1);
+        if (!before(probe)) {
+            hi = probe;
+            break;
+        }
+        lo = probe + 1;
+    }
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (before(mid)) lo = mid + 1;
+        else hi = mid;
+    }
+    found = lo < m && ord[lo] == r;
+    return lo;
+}
+
+// ord and first brought to the snapshot's version from the journal: every journal row (a superset of
+// the rows written since the host half's version) is looked up, or placed, by its key and takes its
+// membership and length as they are now; the other rows keep theirs.  Equal to what host_tables builds.
+void host_patch(const Snapshot& S, ListState& L) {
+    const uint64_t ver = S.version.load();
+    const std::vector<uint32_t> jr = journal_tuple_rows(S, L);
+    const uint64_t m = L.ord.size();
+    std::vector<uint32_t> ord(m + jr.size());
+    std::vector<uint64_t> first(m + jr.size() + 1);
+    first[0] = 0;
+    uint64_t i = 0, k = 0;                                  // old rows taken, new rows written
+    auto keep = [&](uint64_t to) {                          // old rows [i, to) as they are, their entries shifted
+        if (to == i) return;
+        std::copy(L.ord.begin() + i, L.ord.begin() + to, ord.begin() + k);
+        const uint64_t shift = first[k] - L.first[i];       // wraps when the entries move down
+        const uint64_t* of = L.first.data() + i + 1;
+        uint64_t* nf = first.data() + k + 1;
+        for (uint64_t j = 0; j < to - i; ++j) nf[j] = of[j] + shift;
+        k += to - i;
+        i = to;
+    };
+    for (uint32_t r : jr) {
+        bool found;
+        const uint64_t p = ord_place(S, L.ord, i, r, found);
+        keep(p);
+        if (found) ++i;
+        if (in_ord(S, r)) {
+            ord[k] = r;
+            first[k + 1] = first[k] + S.row_edges(r).second;
+            ++k;
+        }
+    }
+    keep(m);
+    ord.resize(k);
+    first.resize(k + 1);
+    if (L.dev_built && !L.dev_desc) {                       // what T was built from stays until the splice
+        L.dev_ord = std::move(L.ord);
+        L.dev_first = std::move(L.first);
+        L.dev_desc = true;
+    }
+    L.ord = std::move(ord);
+    L.first = std::move(first);
+    L.version = ver;
+    L.host_patches += 1;
+    if (!L.dev_built) L.journal_reset(true, ver);           // no device half: the journal is relative to the host half
 }
 
 // T and keys of the current host index, filled on host threads into pinned staging and uploaded
@@ -460,7 +712,128 @@ void device_index(const Snapshot& S, ListState& L, int device) {
     }
     HIP_OK(hipStreamSynchronize(L.stream));
     L.dev_built = true;
+    L.dev_version = L.version;
+    L.dev_n = N;
+    L.keys_n = R;
+    L.keys_cap = std::max<uint64_t>(R, 1);
+    L.dev_builds += 1;
+    L.last_device_ms = 0;
+    L.journal_reset(L.j_valid, L.version);                  // from here on relative to this T
     L.build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The device half brought from dev_version to the host half's version (which is the snapshot's): the
+// segment table of the journal's tuple rows between the two descriptions, the rows' new entries staged
+// in one pinned block, a fresh T' = copy of [0, first segment) + list_splice over the rest, and the
+// new rows' keys.  T and T' live together until the splice is done.  Throws on any failure, the old
+// index untouched: the caller frees it and rebuilds.
+void device_patch(const Snapshot& S, ListState& L) {
+    const uint32_t tile = list_tile();
+    hipStream_t st = L.stream;
+    const std::vector<uint32_t> jr = journal_tuple_rows(S, L);
+    std::vector<LSeg> segs;
+    std::vector<uint32_t> seg_row;
+    const uint64_t N = L.dev_first.back(), newN = L.first.back();
+    if (N != L.dev_n) throw Error{KETO_E_INVALID, "the list index does not match its description"};
+    uint64_t io = 0, in = 0, staged = 0, gone = 0;
+    for (uint32_t r : jr) {
+        bool fo, fn;
+        const uint64_t po = ord_place(S, L.dev_ord, io, r, fo), pn = ord_place(S, L.ord, in, r, fn);
+        io = po + (fo ? 1 : 0);
+        in = pn + (fn ? 1 : 0);
+        const LSeg g{L.dev_first[po], fo ? L.dev_first[po + 1] - L.dev_first[po] : 0, L.first[pn],
+                     fn ? L.first[pn + 1] - L.first[pn] : 0, staged};
+        if (!g.old_len && !g.new_len) continue;
+        // the rows between two segments are the same rows with the same entries: the shift is the same
+        if (g.new_pos + gone != g.old_pos + staged) throw Error{KETO_E_INVALID, "the list journal misses a written row"};
+        if (fn && S.row_edges(r).second != g.new_len) throw Error{KETO_E_INVALID, "the list index is not of this version"};
+        segs.push_back(g);
+        seg_row.push_back(r);
+        staged += g.new_len;
+        gone += g.old_len;
+    }
+    if (newN + gone != N + staged) throw Error{KETO_E_INVALID, "the list journal misses a written row"};
+    const uint64_t R = S.n_rows(), new_keys = R > L.keys_n ? R - L.keys_n : 0, nseg = segs.size();
+    if (nseg > 0xFFFFFFF0ull) throw Error{KETO_E_RANGE, "the list journal holds too many rows"};
+
+    // ---- staging: the segments' new entries, then the new rows' keys
+    struct Staging {
+        void* p;
+        explicit Staging(uint64_t bytes) : p(pinned_take(bytes)) {}
+        ~Staging() { pinned_give(p); }
+    } stage(std::max<uint64_t>(staged + new_keys, 1) * sizeof(uint2));
+    uint2* h = static_cast<uint2*>(stage.p);
+    const unsigned th = staged >= par_min() ? build_threads() : 1u;
+    par_chunks(nseg, th, 64, [&](uint64_t b, uint64_t e, unsigned) {
+        for (uint64_t s = b; s < e; ++s) {
+            if (!segs[s].new_len) continue;
+            const uint32_t row = seg_row[s];
+            const auto ed = S.row_edges(row);
+            uint2* to = h + segs[s].staged;
+            for (uint64_t k = 0; k < segs[s].new_len; ++k) to[k] = make_uint2(row, ed.first[k]);
+        }
+    });
+    for (uint64_t r = L.keys_n; r < R; ++r) h[staged + (r - L.keys_n)] = make_uint2(S.row_key[r].obj, S.row_key[r].rel);
+
+    // ---- device: out of place
+    struct Fresh {
+        uint2* p = nullptr;
+        ~Fresh() {
+            if (p) (void)hipFree(p);
+        }
+    } fresh, fresh_keys;
+    const uint64_t t_entries = (newN + 2) & ~1ull, old_entries = (N + 2) & ~1ull;
+    EventPair ev;
+    HIP_OK(hipEventRecord(ev.a, st));
+    uint64_t keys_cap = L.keys_cap;
+    if (R > L.keys_cap) {                                   // row ids were appended past the allocation
+        keys_cap = R + R / 8 + 1024;
+        HIP_OK(hipMalloc((void**)&fresh_keys.p, keys_cap * sizeof(uint2)));
+        if (L.keys_n)
+            HIP_OK(hipMemcpyAsync(fresh_keys.p, L.keys, L.keys_n * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+    }
+    uint2* keys = fresh_keys.p ? fresh_keys.p : L.keys;
+    if (new_keys)
+        HIP_OK(hipMemcpyAsync(keys + L.keys_n, h + staged, new_keys * sizeof(uint2), hipMemcpyHostToDevice, st));
+    if (nseg) {
+        const uint64_t base = segs[0].new_pos;               // == its old_pos: nothing in front of it moved
+        const uint64_t blocks = (newN - base + tile - 1) / tile;
+        if (blocks > 0x7FFFFFFFull) throw Error{KETO_E_RANGE, "the list splice spans more than 2^31 tiles"};
+        HIP_OK(hipMalloc((void**)&fresh.p, t_entries * sizeof(uint2)));
+        HIP_OK(hipMemsetAsync(fresh.p + newN, 0, (t_entries - newN) * sizeof(uint2), st));
+        if (base) HIP_OK(hipMemcpyAsync(fresh.p, L.T, base * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+        LSeg* d_segs = L.segs.get<LSeg>(nseg);
+        uint2* d_staged = L.staged.get<uint2>(staged);
+        HIP_OK(hipMemcpyAsync(d_segs, segs.data(), nseg * sizeof(LSeg), hipMemcpyHostToDevice, st));
+        if (staged) HIP_OK(hipMemcpyAsync(d_staged, h, staged * sizeof(uint2), hipMemcpyHostToDevice, st));
+        if (blocks) {
+            hipLaunchKernelGGL(list_splice, dim3((uint32_t)blocks), dim3(LIST_THREADS), 0, st, (const uint2*)L.T, N,
+                               (const LSeg*)d_segs, (uint32_t)nseg, (const uint2*)d_staged, staged, base, tile, fresh.p, newN);
+            HIP_OK(hipGetLastError());
+        }
+    }
+    HIP_OK(hipEventRecord(ev.b, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipEventElapsedTime(&L.last_device_ms, ev.a, ev.b));
+    if (fresh.p) {
+        std::swap(L.T, fresh.p);                            // the old T is freed with `fresh`
+        L.bytes = L.bytes - old_entries * sizeof(uint2) + t_entries * sizeof(uint2);
+    }
+    if (fresh_keys.p) {
+        std::swap(L.keys, fresh_keys.p);
+        L.bytes = L.bytes - L.keys_cap * sizeof(uint2) + keys_cap * sizeof(uint2);
+        L.keys_cap = keys_cap;
+    }
+    L.keys_n = std::max(L.keys_n, R);
+    L.dev_n = newN;
+    L.dev_version = L.version;
+    L.drop_dev_desc();
+    L.journal_reset(true, L.version);
+    L.dev_patches += 1;
+    L.last_segments = nseg;
+    L.last_staged = staged;
+    if (L.staged.cap > (64ull << 20)) L.staged.release();   // a big patch's upload buffers do not linger
+    if (L.segs.cap > (64ull << 20)) L.segs.release();
 }
 
 struct Plan {
@@ -581,6 +954,53 @@ void list_plan(const Snapshot& S, ListCache& C, const keto_list_req* reqs, uint3
     });
 }
 
+void list_note_rows(ListCache& C, const uint32_t* rows, uint64_t n, uint64_t ver_before, uint64_t ver_after) noexcept {
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.state) return;
+    ListState& L = *C.state;
+    if (!L.host_built || !L.j_valid) return;
+    if (L.j_upto != ver_before) {                           // a version went by unnoted
+        L.journal_reset(false, 0);
+        return;
+    }
+    try {
+        L.journal.insert(L.journal.end(), rows, rows + n);
+        L.j_upto = ver_after;
+        // raw appends are deduplicated when they outgrow the distinct rows, so the journal stays within
+        // twice its bound; the bound itself is applied to the distinct rows
+        if (L.journal.size() > 2 * L.j_mark + 1024) journal_settle(L);
+    } catch (...) {
+        L.journal_reset(false, 0);
+    }
+}
+
+void list_index_info(const Snapshot& S, ListCache& C, keto_list_index_info_t* out) {
+    std::memset(out, 0, sizeof(*out));
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.state) return;
+    ListState& L = *C.state;
+    journal_settle(L);
+    const uint64_t ver = S.version.load();
+    out->host_built = L.host_built ? 1u : 0u;
+    out->host_current = L.host_built && L.version == ver ? 1u : 0u;
+    out->dev_built = L.dev_built ? 1u : 0u;
+    out->dev_current = L.dev_built && L.host_built && L.dev_version == ver ? 1u : 0u;
+    out->host_version = L.host_built ? L.version : 0;
+    out->dev_version = L.dev_built ? L.dev_version : 0;
+    out->entries = L.dev_built ? L.dev_n : 0;
+    out->device_bytes = L.bytes;
+    out->journal_valid = L.host_built && L.j_valid && L.j_upto == ver && patch_enabled() ? 1u : 0u;
+    out->journal_rows = (uint32_t)std::min<uint64_t>(L.journal.size(), 0xFFFFFFFFull);
+    out->host_builds = L.host_builds;
+    out->host_patches = L.host_patches;
+    out->dev_builds = L.dev_builds;
+    out->dev_patches = L.dev_patches;
+    out->last_segments = L.last_segments;
+    out->last_staged_entries = L.last_staged;
+    out->last_host_ms = L.last_host_ms;
+    out->last_device_ms = L.last_device_ms;
+}
+
 void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, ListResult& out) {
     if (S.n_parts > 1) throw Error{KETO_E_INVALID, "keto_list_batch: a part of a partitioned snapshot holds only some rows"};
     const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
@@ -594,11 +1014,33 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
     const uint32_t tile = list_tile();
     std::lock_guard<std::mutex> lk(C.mu);                    // one list call at a time per snapshot
     HIP_OK(hipSetDevice(V.device));
+    const auto ti = std::chrono::steady_clock::now();
+    auto work = [&] {
+        const ListState* l = C.state.get();
+        return l ? l->host_builds + l->host_patches + l->dev_builds + l->dev_patches : 0;
+    };
+    const uint64_t work0 = work();
     ListState& L = host_index(S, C);
-    if (!L.dev_built) {
-        device_index(S, L, V.device);
-        out.index_ms = L.build_ms;
+    if (L.dev_built && L.dev_version != L.version) {
+        // the device half is behind: spliced from the journal, or -- the journal gone, or any step of
+        // the patch failing -- freed and rebuilt below, where one T is all that is needed
+        bool ok = false;
+        if (L.dev_desc && L.j_valid && L.j_upto == L.version && L.device == V.device && patch_enabled()) {
+            try {
+                device_patch(S, L);
+                ok = true;
+            } catch (const Error&) {
+            } catch (const std::bad_alloc&) {
+            }
+        }
+        if (!ok) {
+            (void)hipGetLastError();
+            L.free_index();
+            L.journal_reset(L.j_valid, L.version);
+        }
     }
+    if (!L.dev_built) device_index(S, L, V.device);
+    if (work() != work0) out.index_ms = ms_since(ti);      // a build's or a patch's time, host part included
     hipStream_t st = L.stream;
 
     // ---- resolve (host threads)
@@ -802,21 +1244,6 @@ void scan_counts(ListState& L, const uint32_t* d_cnt, uint64_t* d_base, uint32_t
     HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cit, d_base, (uint64_t)m + 1, L.stream));
 }
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    EventPair() {
-        HIP_OK(hipEventCreate(&a));
-        if (hipEventCreate(&b) != hipSuccess) {
-            (void)hipEventDestroy(a);
-            throw Error{KETO_E_HIP, "hipEventCreate"};
-        }
-    }
-    ~EventPair() {
-        (void)hipEventDestroy(a);
-        (void)hipEventDestroy(b);
-    }
-};
-
 // the device pass: one count launch (matches, heads, the poison flag), the scans, one host sync, then
 // the HEAD emit of the touched row ids into a pinned block sized exactly.  The caller holds C.mu.
 void scan_device(ListState& L, const LQuery& Q, uint64_t max_rows, DeleteScan& out) {
@@ -936,7 +1363,7 @@ void delete_scan(const Snapshot& S, ListCache& C, const keto_list_req& rq, uint6
         out.scan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return;
     }
-    if (!keyed && S.dev && S.n_parts == 1 && L.dev_built && L.device >= 0) {
+    if (!keyed && S.dev && S.n_parts == 1 && L.dev_built && L.dev_version == L.version && L.device >= 0) {
         out.path = KETO_DELETE_PATH_DEVICE;
         HIP_OK(hipSetDevice(L.device));
         scan_device(*C.state, P.q, max_rows, out);
@@ -1011,26 +1438,34 @@ bool delete_index_patch(const Snapshot& S, ListCache& C, const DeleteScan& sc) n
     try {
         // a list call may have built the device half between the scan and the commit: it is of the
         // scanned version all the same (writes are one at a time)
-        bool dev = L.dev_built && L.host_built && L.version == sc.version && S.dev && S.n_parts == 1;
+        // (a device half behind the scanned version is not kept: a delete never patches from the journal)
+        bool dev = L.dev_built && L.host_built && L.version == sc.version && L.dev_version == sc.version && S.dev &&
+                   S.n_parts == 1;
         if (dev && sc.matches) {
             HIP_OK(hipSetDevice(L.device));
             patch_device(L, sc, L.first.back());
         }
         if (!dev) {
             // no device half to keep: the host half is rebuilt by the next list call, under the shared
-            // lock, instead of here under the exclusive one
+            // lock, instead of here under the exclusive one; the journal goes with the index
             L.host_built = false;
+            L.journal_reset(false, 0);
             if (L.device >= 0) {
                 (void)hipSetDevice(L.device);
                 L.free_index();
             }
+            L.drop_dev_desc();
             return false;
         }
         host_tables(S, L);
         L.dev_built = true;
+        L.dev_version = L.version;
+        L.dev_n = L.first.back();
+        L.dev_patches += 1;
         return true;
     } catch (...) {
         L.host_built = false;
+        L.journal_reset(false, 0);
         if (L.device >= 0) {
             (void)hipSetDevice(L.device);
             L.free_index();

@@ -35,6 +35,14 @@ void list_plan(const Snapshot& s, ListCache& c, const keto_list_req* reqs, uint3
 void list_batch(Snapshot& s, ListCache& c, const keto_list_req* reqs, uint32_t n, ListResult& out);
 uint64_t list_device_bytes(ListCache& c);   // device memory of the list index (0 before the first list_batch)
 
+// The journal of written rows.  keto_snapshot_apply, holding the snapshot's lock exclusive, after the
+// commit that took the version from ver_before to ver_after: notes the rows it changed.  Nothing is
+// noted without index state; past KETO_LIST_PATCH_MAX_ROWS distinct rows, with KETO_LIST_PATCH=0, or when
+// a version went by unnoted the journal is invalid and the next list call rebuilds the index.
+void list_note_rows(ListCache& c, const uint32_t* rows, uint64_t n, uint64_t ver_before, uint64_t ver_after) noexcept;
+// keto_list_index_info: the caller holds the snapshot's lock shared; builds nothing
+void list_index_info(const Snapshot& s, ListCache& c, keto_list_index_info_t* out);
+
 // keto_snapshot_delete_query: the rows a whereQuery / whereSubject touches (list.hip)
 struct DeleteScan {
     std::vector<uint32_t> rows;      // the tuple rows that lose a tuple, ascending and distinct
