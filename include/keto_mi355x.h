@@ -769,6 +769,80 @@ typedef struct {
 } keto_delete_info;
 int keto_snapshot_delete_query(keto_snapshot* s, const keto_list_req* query, keto_delete_info* out /* may be NULL */);
 
+/* ---- Reverse lookup: the objects a subject has a relation on (repo:keto_amd/csrc/list.hip) ----
+ * keto_lookup_objects_batch answers, per query, "which objects o of `namespace_` does `subject` have
+ * `relation` on": a question the reference has no call for -- there it costs one
+ * check.(*Engine).SubjectIsAllowed (internal/check/engine.go:116-123) per candidate object.  Query i
+ * answers with the row ids of the tuple rows (namespace_, o, relation) whose check against `subject`,
+ * at the same request and global max-depth, is allowed: for every non-empty o that is keto_check_batch
+ * on namespace_:o#relation@subject returning allowed with KETO_CHECK_OK; a tuple row whose object is
+ * the empty string is checked as that one row, by row id (a named request with an empty object would
+ * be a wildcard query over every object instead).  Rows come in key order, i.e. in ascending byte order of o; the page is rows
+ * [(page-1) * size, page * size) of them with page = max(page, 1), next_page and the total follow the
+ * list rule (above), the total being the allowed objects of the whole query.  The caller decodes a row
+ * with keto_subject_fields(s, NULL, {row | 0x80000000}, ...), exactly as for list tuples; row ids stay
+ * decodable after later writes.
+ *
+ * Nothing is traversed backwards: the candidates of a query are the distinct tuple rows of its
+ * namespace and relation, taken from the list index in key order (the HEAD passes that
+ * keto_snapshot_delete_query uses), and every candidate is checked forwards by the check kernels, on
+ * the device, as a keto_check_batch_rows_device request.  An object with no tuple at that relation
+ * can never be allowed (the check reads the top-level row's tuples, engine.go:82-114), so the tuple
+ * rows are the complete candidate set, and the set returned is exactly the set this engine's check
+ * allows.  Candidates, requests and decisions stay in device memory; the page of allowed row ids is
+ * all that comes back.  A subject the snapshot does not know is not an error: every check is false
+ * (KETO_LOOKUP_OK, total 0).  A poisoned top-level row is simply a candidate: the check truncates it
+ * at its first poisoned page, as it does for keto_check_batch.
+ *
+ * namespace_ and relation are both required and taken literally, as a check request's are.  An empty
+ * namespace_ or relation, or a subject set with an empty field, would be a wildcard check, which needs
+ * batch-local rows: KETO_LOOKUP_UNSUPPORTED for that query (ask keto_check_batch); the other queries
+ * of the batch are answered as usual.
+ *
+ * Errors, as for lists: a host-only snapshot is KETO_E_HIP (whatever n is), any part of a partitioned
+ * upload (n_parts > 1) KETO_E_INVALID; n = 0 gives count 0 and offsets {0}.  More than
+ * KETO_LOOKUP_MAX_CANDIDATES candidates (environment, default 2^28) over the queries of one call fail
+ * the call with KETO_E_INVALID before any check runs.  Candidates are checked in chunks of
+ * KETO_LOOKUP_CHUNK (environment, default 2^22, at least 64).  The call holds the snapshot's lock
+ * shared from start to end, so every decision belongs to one version, and runs one at a time per
+ * snapshot with the list calls, whose index and stream it shares (the first call on a version builds
+ * or patches the list index exactly as keto_list_batch does).  Device memory beyond the list index:
+ * 5 B per candidate (row id and decision), 16 B per candidate of a chunk (its request; the check
+ * keeps a translated copy of as many), 4 B per emitted row; the candidate, decision and request
+ * buffers are kept for the next call up to 256 MB each and freed at the end of a call past that (they
+ * are not counted in keto_snapshot_stats.device_bytes).  The result owns a block of the pinned
+ * pool sized exactly after the totals (a huge page_size allocates nothing) and holds no reference to
+ * the snapshot: it stays readable after keto_snapshot_apply and keto_snapshot_release, until
+ * keto_looked_free. */
+#define KETO_LOOKUP_OK 0                 /* rows, next_page, total equal per-object SubjectIsAllowed */
+#define KETO_LOOKUP_UNKNOWN_NAMESPACE 1  /* query namespace unknown: every check is false; no rows, total 0 */
+#define KETO_LOOKUP_UNDECIDED 2          /* >= 1 candidate's check was KETO_UNDECIDED: no rows, total 0; `undecided` says how many */
+#define KETO_LOOKUP_UNSUPPORTED 3        /* empty namespace or relation, or a subject set with an empty field
+                                            (wildcard checks need batch-local rows): ask keto_check_batch */
+typedef struct {
+    keto_str namespace_, relation;   /* both required, taken literally as a check request's are */
+    keto_subject subject;
+    int32_t  max_depth;              /* <= 0 or > global -> global, as keto_check_req */
+    uint32_t page_size;              /* 0 -> the snapshot's page_size */
+    uint32_t page;                   /* 0 = page 1 */
+} keto_lookup_req;
+typedef struct keto_looked keto_looked;
+int keto_lookup_objects_batch(keto_snapshot* s, const keto_lookup_req* reqs, uint32_t n,
+                              int32_t global_max_depth, keto_looked** out);
+void keto_looked_free(keto_looked*);                       /* NULL is fine */
+uint32_t        keto_looked_count(const keto_looked*);     /* n */
+const uint32_t* keto_looked_rows(const keto_looked*, uint64_t* total_out);  /* row ids (NULL when there are none) */
+const uint64_t* keto_looked_offsets(const keto_looked*);    /* n+1; query i = rows[off[i], off[i+1]) */
+const uint8_t*  keto_looked_status(const keto_looked*);     /* n x KETO_LOOKUP_* */
+const uint64_t* keto_looked_next_page(const keto_looked*);  /* the list rule: 0 on the last page, when nothing matches, or past the end */
+const uint64_t* keto_looked_totals(const keto_looked*);     /* allowed objects of the whole query */
+const uint64_t* keto_looked_candidates(const keto_looked*); /* rows checked for the query */
+const uint64_t* keto_looked_undecided(const keto_looked*);  /* of them: checks that ended KETO_UNDECIDED */
+/* of the call that made the result: index_ms = the list index (re)built first (0 when it was current);
+ * HIP events on the list stream: candidates_ms = the HEAD count, scan and emit, check_ms = the
+ * chunks' requests and checks, emit_ms = the count, scan and emit of the allowed rows and their copy */
+int keto_looked_timing(const keto_looked*, float* index_ms, float* candidates_ms, float* check_ms, float* emit_ms);
+
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,
  * internal/relationtuple/definitions.go:40-42,102-117) straight from the node arena without a text

@@ -839,3 +839,101 @@ func (s *Snapshot) ListBatch(qs []ListQuery) ([]ListResult, error) {
 	}
 	return out, nil
 }
+
+// Lookup statuses of LookupObjects (KETO_LOOKUP_*).
+const (
+	LookupOK               = uint8(C.KETO_LOOKUP_OK)
+	LookupUnknownNamespace = uint8(C.KETO_LOOKUP_UNKNOWN_NAMESPACE) // every check is false: no objects
+	LookupUndecided        = uint8(C.KETO_LOOKUP_UNDECIDED)         // a candidate's check exceeded the engine's limits: check the objects one by one
+	LookupUnsupported      = uint8(C.KETO_LOOKUP_UNSUPPORTED)       // an empty field (a wildcard check): ask CheckBatch
+)
+
+// LookupQuery asks which objects of Namespace the Subject has Relation on (keto_lookup_req).  Namespace
+// and Relation are required; MaxDepth <= 0 or past the global maximum is the global maximum, as for a
+// check; PageSize 0 is the snapshot's page size and Page 0 the first page.
+type LookupQuery struct {
+	Namespace, Relation string
+	Subject             relationtuple.Subject
+	MaxDepth            int
+	PageSize, Page      uint32
+}
+
+// LookupResult is one query's page of objects in ascending byte order, the next page's number (0: the
+// last page), the count of all allowed objects, the rows that were checked and the checks among them
+// that ended undecided.  Objects are set only when Status is LookupOK.
+type LookupResult struct {
+	Status     uint8
+	Objects    []string
+	NextPage   uint64
+	Total      uint64
+	Candidates uint64
+	Undecided  uint64
+}
+
+// LookupObjects answers, for many queries, the reverse of a check: the objects o for which
+// check.(*Engine).SubjectIsAllowed (internal/check/engine.go:116-123) on Namespace:o#Relation@Subject
+// is true (keto_lookup_objects_batch).  The reference has no such call; there it takes one check per
+// object.  The rows come back as row ids; their object strings are read with keto_subject_fields, one
+// call for the batch.  Not for a Partition: a part holds only some rows (KETO_E_INVALID).
+func (s *Snapshot) LookupObjects(qs []LookupQuery, globalMax int) ([]LookupResult, error) {
+	n := len(qs)
+	if n == 0 {
+		return nil, nil
+	}
+	var m cmem
+	defer m.free()
+	total := 0
+	for i := range qs {
+		total += len(qs[i].Namespace) + len(qs[i].Relation) + subjectLen(qs[i].Subject)
+	}
+	m.strings(total)
+	cr := (*C.keto_lookup_req)(m.alloc(n * int(C.sizeof_keto_lookup_req)))
+	cs := unsafe.Slice(cr, n)
+	for i := range qs {
+		q := &qs[i]
+		if q.Subject == nil {
+			return nil, &Error{Code: int(C.KETO_E_INVALID), Msg: "LookupObjects: a query needs a subject"}
+		}
+		cs[i] = C.keto_lookup_req{namespace_: m.s(q.Namespace), relation: m.s(q.Relation), subject: m.subject(q.Subject),
+			max_depth: C.int32_t(q.MaxDepth), page_size: C.uint32_t(q.PageSize), page: C.uint32_t(q.Page)}
+	}
+	var l *C.keto_looked
+	if rc := C.keto_lookup_objects_batch(s.h, cr, C.uint32_t(n), C.int32_t(globalMax), &l); rc != C.KETO_OK {
+		return nil, lastErr(rc)
+	}
+	defer C.keto_looked_free(l)
+	var count C.uint64_t
+	rp := C.keto_looked_rows(l, &count)
+	off := unsafe.Slice(C.keto_looked_offsets(l), n+1)
+	status := unsafe.Slice(C.keto_looked_status(l), n)
+	next := unsafe.Slice(C.keto_looked_next_page(l), n)
+	totals := unsafe.Slice(C.keto_looked_totals(l), n)
+	cands := unsafe.Slice(C.keto_looked_candidates(l), n)
+	und := unsafe.Slice(C.keto_looked_undecided(l), n)
+	var refs []uint32
+	if rp != nil && count > 0 {
+		rows := unsafe.Slice(rp, int(count)) // the result's memory: read before keto_looked_free
+		refs = make([]uint32, len(rows))
+		for i, r := range rows {
+			refs[i] = uint32(r) | 0x80000000 // the row as the subject set of its namespace, object and relation
+		}
+	}
+	subjects, err := s.subjects(nil, refs, &m)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]LookupResult, n)
+	for i := 0; i < n; i++ {
+		out[i] = LookupResult{Status: uint8(status[i]), NextPage: uint64(next[i]), Total: uint64(totals[i]),
+			Candidates: uint64(cands[i]), Undecided: uint64(und[i])}
+		if out[i].Status != LookupOK {
+			continue
+		}
+		page := subjects[int(off[i]):int(off[i+1])]
+		out[i].Objects = make([]string, len(page))
+		for k, sub := range page {
+			out[i].Objects[k] = sub.(*relationtuple.SubjectSet).Object
+		}
+	}
+	return out, nil
+}

@@ -47,9 +47,13 @@ EXPORTS = [
     "keto_list_batch", "keto_listed_free", "keto_listed_count", "keto_listed_tuples", "keto_listed_offsets",
     "keto_listed_status", "keto_listed_next_page", "keto_listed_totals", "keto_listed_timing", "keto_list_plan",
     "keto_snapshot_delete_query", "keto_list_index_info",
+    "keto_lookup_objects_batch", "keto_looked_free", "keto_looked_count", "keto_looked_rows", "keto_looked_offsets",
+    "keto_looked_status", "keto_looked_next_page", "keto_looked_totals", "keto_looked_candidates",
+    "keto_looked_undecided", "keto_looked_timing",
 ]
 DELETE_PATH_HOST, DELETE_PATH_DEVICE = 0, 1
 LIST_OK, LIST_NOT_FOUND, LIST_UNDECIDED = 0, 1, 2
+LOOKUP_OK, LOOKUP_UNKNOWN_NAMESPACE, LOOKUP_UNDECIDED, LOOKUP_UNSUPPORTED = 0, 1, 2, 3
 ENC_PROTO, ENC_JSON = 0, 1
 ENCODINGS = {"proto": ENC_PROTO, "json": ENC_JSON}
 PART_SHARED, PART_MIGRATE = 0, 1
@@ -133,6 +137,11 @@ class KExpandReq(C.Structure):
 class KListReq(C.Structure):
     _fields_ = [("namespace_", KStr), ("object", KStr), ("relation", KStr), ("has_subject", C.c_uint8),
                 ("subject", KSubject), ("page_size", C.c_uint32), ("page", C.c_uint32)]
+
+
+class KLookupReq(C.Structure):
+    _fields_ = [("namespace_", KStr), ("relation", KStr), ("subject", KSubject), ("max_depth", C.c_int32),
+                ("page_size", C.c_uint32), ("page", C.c_uint32)]
 
 
 class KListPlan(C.Structure):
@@ -256,6 +265,18 @@ def load():
             f.restype = C.c_void_p
             f.argtypes = [C.c_void_p]
         lib.keto_listed_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    if hasattr(lib, "keto_lookup_objects_batch"):
+        lib.keto_looked_free.restype = None
+        lib.keto_looked_free.argtypes = [C.c_void_p]
+        lib.keto_looked_count.restype = C.c_uint32
+        lib.keto_looked_count.argtypes = [C.c_void_p]
+        lib.keto_looked_rows.restype = C.c_void_p
+        lib.keto_looked_rows.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        for f in (lib.keto_looked_offsets, lib.keto_looked_status, lib.keto_looked_next_page, lib.keto_looked_totals,
+                  lib.keto_looked_candidates, lib.keto_looked_undecided):
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p]
+        lib.keto_looked_timing.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 4
     lib.keto_route_work_bytes.argtypes = [C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
@@ -914,6 +935,56 @@ class Snapshot:
         dec = self.decode_list_tuples(tup)
         return [(int(status[i]), dec[int(offs[i]):int(offs[i + 1])], str(int(nxt[i])) if nxt[i] else "", int(tot[i]))
                 for i in range(len(queries))]
+
+    # ------------------------------------------------------------------ reverse lookup
+    def lookup_objects_raw(self, queries, global_max_depth=5):
+        """keto_lookup_objects_batch.  queries: (namespace, relation, subject, max_depth, page_size, page)
+        with subject as in check_batch, page_size 0 = the snapshot's and page 0 = the first -> a dict of
+        arrays copied out of the keto_looked handle, which is freed here: status[n], offsets[n+1], rows
+        (uint32 row ids), next_page[n], totals[n], candidates[n], undecided[n] and timing = (index_ms,
+        candidates_ms, check_ms, emit_ms)."""
+        keep = _Keep()
+        n = len(queries)
+        arr = (KLookupReq * max(1, n))()
+        for k, (ns, rel, sub, depth, size, page) in enumerate(queries):
+            arr[k].namespace_ = keep.s(ns)
+            arr[k].relation = keep.s(rel)
+            arr[k].subject = subject_struct(keep, sub)
+            arr[k].max_depth = depth
+            arr[k].page_size = size
+            arr[k].page = page
+        h = C.c_void_p()
+        _check(self.lib.keto_lookup_objects_batch(self.h, arr, C.c_uint32(n), C.c_int32(global_max_depth), C.byref(h)))
+        try:
+            assert self.lib.keto_looked_count(h) == n
+            total = C.c_uint64()
+            p = self.lib.keto_looked_rows(h, C.byref(total))
+            get = lambda f, nbytes, dt: np.frombuffer(C.string_at(f(h), nbytes), dtype=dt).copy()
+            out = {"status": get(self.lib.keto_looked_status, n, np.uint8),
+                   "offsets": get(self.lib.keto_looked_offsets, 8 * (n + 1), np.uint64),
+                   "next_page": get(self.lib.keto_looked_next_page, 8 * n, np.uint64),
+                   "totals": get(self.lib.keto_looked_totals, 8 * n, np.uint64),
+                   "candidates": get(self.lib.keto_looked_candidates, 8 * n, np.uint64),
+                   "undecided": get(self.lib.keto_looked_undecided, 8 * n, np.uint64),
+                   "rows": (np.frombuffer(C.string_at(p, 4 * total.value), dtype=np.uint32).copy() if total.value
+                            else np.zeros(0, dtype=np.uint32))}
+            ms = [C.c_float() for _ in range(4)]
+            _check(self.lib.keto_looked_timing(h, *[C.byref(x) for x in ms]))
+            out["timing"] = tuple(x.value for x in ms)
+        finally:
+            self.lib.keto_looked_free(h)
+        return out
+
+    def lookup_objects(self, queries, global_max_depth=5):
+        """Which objects of a namespace does a subject have a relation on: queries as in
+        lookup_objects_raw -> per query (status, [object strings in byte order], next page token ("" = last
+        page), total allowed objects, candidates checked, undecided checks)."""
+        r = self.lookup_objects_raw(queries, global_max_depth)
+        objs = [f[2] for f in self.subject_fields(r["rows"] | np.uint32(0x80000000))] if len(r["rows"]) else []
+        offs = r["offsets"]
+        return [(int(r["status"][i]), objs[int(offs[i]):int(offs[i + 1])],
+                 str(int(r["next_page"][i])) if r["next_page"][i] else "", int(r["totals"][i]),
+                 int(r["candidates"][i]), int(r["undecided"][i])) for i in range(len(queries))]
 
     def subject_fields(self, refs, arena=None):
         """keto_subject_fields: per subject reference ("id", id) or ("set", namespace, object, relation)."""

@@ -1398,6 +1398,57 @@ int keto_listed_timing(const keto_listed* l, float* index_ms, float* scan_ms) {
     });
 }
 
+// ---- keto_lookup_objects_batch: the objects a subject has a relation on (list.hip)
+struct keto_looked {
+    LookupResult r;                         // r.rows: a block of the pinned pool, or NULL
+    ~keto_looked() { pinned_give(r.rows); }
+};
+
+int keto_lookup_objects_batch(keto_snapshot* h, const keto_lookup_req* reqs, uint32_t n, int32_t global_max_depth,
+                              keto_looked** out) {
+    return guarded([&] {
+        if (!h || !out || (n && !reqs)) throw Error{KETO_E_INVALID, "NULL argument"};
+        *out = nullptr;
+        std::shared_lock<RwGate> lk(h->s->rw);        // one version from the candidates to the page
+        auto l = std::make_unique<keto_looked>();
+        lookup_objects(*h->s, h->list, reqs, n, global_max_depth, l->r);
+        *out = l.release();
+        return KETO_OK;
+    });
+}
+
+void keto_looked_free(keto_looked* l) { delete l; }
+
+uint32_t keto_looked_count(const keto_looked* l) { return l ? (uint32_t)l->r.status.size() : 0; }
+
+const uint32_t* keto_looked_rows(const keto_looked* l, uint64_t* total_out) {
+    if (total_out) *total_out = l ? l->r.offsets.back() : 0;
+    return l ? l->r.rows : nullptr;
+}
+
+const uint64_t* keto_looked_offsets(const keto_looked* l) { return l ? l->r.offsets.data() : nullptr; }
+
+const uint8_t* keto_looked_status(const keto_looked* l) { return l ? l->r.status.data() : nullptr; }
+
+const uint64_t* keto_looked_next_page(const keto_looked* l) { return l ? l->r.next_page.data() : nullptr; }
+
+const uint64_t* keto_looked_totals(const keto_looked* l) { return l ? l->r.totals.data() : nullptr; }
+
+const uint64_t* keto_looked_candidates(const keto_looked* l) { return l ? l->r.candidates.data() : nullptr; }
+
+const uint64_t* keto_looked_undecided(const keto_looked* l) { return l ? l->r.undecided.data() : nullptr; }
+
+int keto_looked_timing(const keto_looked* l, float* index_ms, float* candidates_ms, float* check_ms, float* emit_ms) {
+    return guarded([&] {
+        if (!l) throw Error{KETO_E_INVALID, "NULL argument"};
+        if (index_ms) *index_ms = l->r.index_ms;
+        if (candidates_ms) *candidates_ms = l->r.candidates_ms;
+        if (check_ms) *check_ms = l->r.check_ms;
+        if (emit_ms) *emit_ms = l->r.emit_ms;
+        return KETO_OK;
+    });
+}
+
 int keto_list_index_info(const keto_snapshot* h, keto_list_index_info_t* out) {
     return guarded([&] {
         if (!h || !out) throw Error{KETO_E_INVALID, "NULL argument"};

@@ -48,6 +48,14 @@
 // before it) and a copy of [hi, N); keys[] stays (a delete adds no row), ord / first are rebuilt on
 // the host.  Without a current device index the host scans the candidate rows ord[p0, p1) instead,
 // and no index is built for a delete.
+//
+// keto_lookup_objects_batch (which objects of a namespace does a subject have a relation on; the
+// reference would run one SubjectIsAllowed, internal/check/engine.go:116-123, per object) uses the HEAD
+// passes too: the heads of a namespace + relation query without a subject are its tuple rows in key
+// order, the only objects the check can allow.  lookup_make_reqs turns a chunk of them into row-id check
+// requests, device_check_rows decides them into one byte each, and lookup_count / scan / lookup_emit
+// compact the allowed ones, in order, into the page -- candidates, requests and decisions stay on the
+// device.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -338,6 +346,150 @@ LIST_EMIT_KERNEL(list_emit_heads, LIST_HEAD)
 LIST_EMIT_KERNEL(list_emit_keep, LIST_KEEP)
 #undef LIST_EMIT_KERNEL
 
+// ---- keto_lookup_objects_batch: the candidates of a query are the HEAD pass's rows (above); what
+// follows turns them into check requests and compacts the allowed ones, in order, into the page.
+struct LSubj {           // the subject of a lookup query in the row-id form of keto_check_ids
+    uint32_t target, flags;
+    int32_t max_depth;
+    uint32_t pad;
+};
+
+// The 16-B requests of candidates [c0, c0 + m) of cand[] (query-major): a candidate's query is the
+// last one whose first candidate qoff[q] is at or before it (empty queries share their successor's
+// offset and are passed over).  One 16-B store per lane.
+__global__ void __launch_bounds__(LIST_THREADS)
+lookup_make_reqs(const uint32_t* __restrict__ cand, const uint64_t* __restrict__ qoff, uint32_t nq,
+                 const LSubj* __restrict__ subj, uint64_t c0, uint32_t m, uint4* __restrict__ reqs) {
+    const uint32_t i = blockIdx.x * LIST_THREADS + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t g = c0 + i;
+    uint32_t lo = 0, hi = nq;                              // qoff[lo] <= g; qoff[hi] > g or hi == nq
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (qoff[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const LSubj s = subj[lo];
+    reqs[i] = make_uint4(cand[g], s.target, s.flags, (uint32_t)s.max_depth);
+}
+
+// The four decisions a lane holds of the wave's 256-candidate step starting at the 4-aligned p0:
+// bytes e0 = p0 + 4 lane .. e0 + 3, those inside the wave's range [ws, we) as bit k of `allowed`
+// (decision 1) and `undecided` (KETO_UNDECIDED).  dec[] is padded, so the 4-B load of a word whose
+// last bytes are past the range stays inside it.
+__device__ inline void lookup_quad(const uint8_t* __restrict__ dec, uint64_t p0, uint32_t lane, uint64_t ws, uint64_t we,
+                                   uint32_t& allowed, uint32_t& undecided) {
+    const uint64_t e0 = p0 + 4ull * lane;
+    allowed = undecided = 0;
+    if (e0 < we && e0 + 4 > ws) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(dec + e0);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint64_t e = e0 + k;
+            if (e < ws || e >= we) continue;
+            const uint32_t b = (w >> (8 * k)) & 0xFFu;
+            allowed |= (b == 1u ? 1u : 0u) << k;
+            undecided |= (b == KETO_UNDECIDED ? 1u : 0u) << k;
+        }
+    }
+}
+
+// the wave's range of candidates of item `it`: a quarter of the tile [ia, ib) of the query's candidates
+__device__ inline void lookup_range(const uint64_t* __restrict__ qoff, const LItem& it, uint32_t tile, uint32_t wave,
+                                    uint64_t& ws, uint64_t& we) {
+    const uint32_t quarter = tile / LIST_WAVES;
+    const uint64_t ia = qoff[it.q] + (uint64_t)it.tile * tile, ib = min(ia + tile, qoff[it.q + 1]);
+    ws = min(ia + (uint64_t)wave * quarter, ib);
+    we = min(ws + quarter, ib);
+}
+
+// one block per (query, tile of its candidates): the allowed decisions of the item and of its four
+// waves; undecided ones are added to the query's counter (a count, no order hangs on it)
+__global__ void __launch_bounds__(LIST_THREADS)
+lookup_count(const uint8_t* __restrict__ dec, const uint64_t* __restrict__ qoff, const LItem* __restrict__ items,
+             uint32_t tile, uint32_t* __restrict__ cnt, uint32_t* __restrict__ wcnt,
+             unsigned long long* __restrict__ qund) {
+    __shared__ uint32_t wsum[LIST_WAVES];
+    __shared__ uint32_t wund[LIST_WAVES];
+    const LItem it = items[blockIdx.x];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint64_t ws, we;
+    lookup_range(qoff, it, tile, wave, ws, we);
+    uint32_t c = 0, u = 0;
+    for (uint64_t p0 = ws & ~3ull; p0 < we; p0 += 256) {
+        uint32_t a, d;
+        lookup_quad(dec, p0, lane, ws, we, a, d);
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) c += __popcll(__ballot((a >> k) & 1u));
+        if (__ballot(d != 0u) != 0ull) {
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) u += __popcll(__ballot((d >> k) & 1u));
+        }
+    }
+    if (lane == 0) {
+        wsum[wave] = c;
+        wund[wave] = u;
+    }
+    __syncthreads();
+    if (threadIdx.x < LIST_WAVES) wcnt[(uint64_t)blockIdx.x * LIST_WAVES + threadIdx.x] = wsum[threadIdx.x];
+    if (threadIdx.x == 0) {
+        uint32_t s = 0, un = 0;
+        for (uint32_t w = 0; w < LIST_WAVES; ++w) {
+            s += wsum[w];
+            un += wund[w];
+        }
+        cnt[blockIdx.x] = s;
+        if (un) atomicAdd(qund + it.q, (unsigned long long)un);
+    }
+}
+
+// items whose rank range misses the query's window exit; the others recompute their decisions and
+// store the candidates whose rank = item base + waves before + allowed before in the wave falls in
+// the window at out[offset + rank - window start].  A lane's four candidates follow one another, so
+// the allowed ones before a lane's k-th are those of the lower lanes (all four bits) and its own
+// lower bits.
+__global__ void __launch_bounds__(LIST_THREADS)
+lookup_emit(const uint8_t* __restrict__ dec, const uint32_t* __restrict__ cand, const uint64_t* __restrict__ qoff,
+            const LItem* __restrict__ items, uint32_t tile, const uint32_t* __restrict__ cnt,
+            const uint32_t* __restrict__ wcnt, const uint64_t* __restrict__ base, const uint32_t* __restrict__ ioff,
+            const LWindow* __restrict__ wins, uint32_t* __restrict__ out, uint64_t out_n) {
+    const LItem it = items[blockIdx.x];
+    const LWindow W = wins[it.q];
+    if (W.whi <= W.wlo) return;
+    const uint64_t r0 = base[blockIdx.x] - base[ioff[it.q]];
+    if (r0 + cnt[blockIdx.x] <= W.wlo || r0 >= W.whi) return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint64_t ws, we;
+    lookup_range(qoff, it, tile, wave, ws, we);
+    uint64_t r = r0;
+    for (uint32_t w = 0; w < wave; ++w) r += wcnt[(uint64_t)blockIdx.x * LIST_WAVES + w];
+    if (r + wcnt[(uint64_t)blockIdx.x * LIST_WAVES + wave] <= W.wlo) return;
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (uint64_t p0 = ws & ~3ull; p0 < we && r < W.whi; p0 += 256) {
+        uint32_t a, d;
+        lookup_quad(dec, p0, lane, ws, we, a, d);
+        uint64_t k0 = r;
+        uint32_t step = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            const uint64_t b = __ballot((a >> k) & 1u);
+            k0 += __popcll(b & below);
+            step += __popcll(b);
+        }
+        const uint64_t e0 = p0 + 4ull * lane;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; ++k) {
+            if (!((a >> k) & 1u)) continue;
+            const uint64_t rank = k0 + __popc(a & ((1u << k) - 1u));
+            if (rank >= W.wlo && rank < W.whi) {
+                const uint64_t at = W.off + (rank - W.wlo);
+                if (at < out_n) out[at] = cand[e0 + k];
+            }
+        }
+        r += step;
+    }
+}
+
 // One changed tuple row of a splice: its entries [old_pos, old_pos + old_len) of T become
 // [new_pos, new_pos + new_len) of T', taken from the staged block at `staged`.  A new row has
 // old_len = 0 at its insertion point, a row that left the index new_len = 0.  Sorted by position (old
@@ -439,6 +591,15 @@ struct ListState {
     LBuf qs, items, ioff, cnt, wcnt, base, tot, qpoison, qpage, wins, out, tmp;
     LBuf hcnt, hwcnt, hbase;         // the delete scan's head counts (keto_snapshot_delete_query)
     LBuf segs, staged;               // the splice's segment table and new entries
+    // keto_lookup_objects_batch: candidates (4 B each) and their decisions (1 B each), a chunk's check
+    // requests (16 B each), the queries' candidate offsets, subjects and undecided counts
+    LBuf lk_cand, lk_dec, lk_reqs, lk_qoff, lk_subj, lk_und;
+    hipEvent_t lk_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // a lookup's phase marks on `stream`
+    // a big lookup's candidate, decision and request buffers do not linger (as the splice's upload buffers)
+    void lookup_trim() {
+        for (LBuf* b : {&lk_cand, &lk_dec, &lk_reqs})
+            if (b->cap > (256ull << 20)) b->release();
+    }
     // The device half may lag the host half (a keto_list_plan or a delete's host scan patched the host
     // half first): then dev_ord / dev_first are the ord / first T was built from, moved here by that
     // patch.  Otherwise ord / first describe T.
@@ -480,6 +641,8 @@ struct ListState {
         if (device < 0) return;
         (void)hipSetDevice(device);
         free_index();
+        for (hipEvent_t x : lk_ev)
+            if (x) (void)hipEventDestroy(x);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -1001,19 +1164,13 @@ void list_index_info(const Snapshot& S, ListCache& C, keto_list_index_info_t* ou
     out->last_device_ms = L.last_device_ms;
 }
 
-void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, ListResult& out) {
-    if (S.n_parts > 1) throw Error{KETO_E_INVALID, "keto_list_batch: a part of a partitioned snapshot holds only some rows"};
-    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
-    out.status.assign(n, KETO_LIST_OK);
-    out.offsets.assign((uint64_t)n + 1, 0);
-    out.next_page.assign(n, 0);
-    out.totals.assign(n, 0);
-    out.tuples = nullptr;
-    out.index_ms = out.scan_ms = 0;
-    if (n == 0) return;
-    const uint32_t tile = list_tile();
-    std::lock_guard<std::mutex> lk(C.mu);                    // one list call at a time per snapshot
-    HIP_OK(hipSetDevice(V.device));
+namespace {
+
+// The list index of the snapshot's version on `device`, both halves: built, patched from the journal
+// or rebuilt as need be.  index_ms: a build's or a patch's time, host part included (left as it is
+// when the index was current).  The caller holds C.mu and S.rw shared.
+ListState& current_index(const Snapshot& S, ListCache& C, int device, float& index_ms) {
+    HIP_OK(hipSetDevice(device));
     const auto ti = std::chrono::steady_clock::now();
     auto work = [&] {
         const ListState* l = C.state.get();
@@ -1025,7 +1182,7 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
         // the device half is behind: spliced from the journal, or -- the journal gone, or any step of
         // the patch failing -- freed and rebuilt below, where one T is all that is needed
         bool ok = false;
-        if (L.dev_desc && L.j_valid && L.j_upto == L.version && L.device == V.device && patch_enabled()) {
+        if (L.dev_desc && L.j_valid && L.j_upto == L.version && L.device == device && patch_enabled()) {
             try {
                 device_patch(S, L);
                 ok = true;
@@ -1039,8 +1196,112 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
             L.journal_reset(L.j_valid, L.version);
         }
     }
-    if (!L.dev_built) device_index(S, L, V.device);
-    if (work() != work0) out.index_ms = ms_since(ti);      // a build's or a patch's time, host part included
+    if (!L.dev_built) device_index(S, L, device);
+    if (work() != work0) index_ms = ms_since(ti);
+    return L;
+}
+
+void scan_counts(ListState& L, const uint32_t* d_cnt, uint64_t* d_base, uint32_t m);
+
+// The count pass of a batch of queries over the index, shared by lists (MATCH counts) and lookups (HEAD
+// counts): the items per query, the query groups of at most LIST_GROUP_ITEMS items (a single query may
+// exceed it; the item buffers hold one group at a time), and per group the items' upload, the count
+// kernel, the scan of its counts and the queries' totals into d_tot.
+struct GroupedCount {
+    ListState& L;
+    hipStream_t st;
+    uint32_t tile;
+    bool heads;                      // list_count_heads into hcnt / hwcnt / hbase, else list_count into cnt / wcnt / base
+    const LQuery* d_qs;
+    uint64_t* d_tot;
+    uint32_t* d_qpoison;
+    std::vector<uint64_t> qitems;    // n + 1: items before each query
+    std::vector<uint32_t> groups;    // query boundaries of the groups
+    std::vector<LItem> items;
+    std::vector<uint32_t> ioff;
+
+    GroupedCount(ListState& l, uint32_t tile_, bool heads_, const std::vector<LQuery>& qs, const LQuery* dq, uint64_t* dt,
+                 uint32_t* dp, const char* who)
+        : L(l), st(l.stream), tile(tile_), heads(heads_), d_qs(dq), d_tot(dt), d_qpoison(dp) {
+        const uint32_t n = (uint32_t)qs.size();
+        const std::string too_many = std::string(who) + ": a query spans more than 2^32 tiles";
+        qitems.assign((uint64_t)n + 1, 0);
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint64_t k = (qs[i].hi - qs[i].lo + tile - 1) / tile;
+            if (k > 0xFFFFFFF0ull) throw Error{KETO_E_RANGE, too_many};
+            qitems[i + 1] = qitems[i] + k;
+        }
+        groups.push_back(0);
+        for (uint32_t i = 0; i < n; ++i)
+            if (qitems[i + 1] - qitems[groups.back()] > LIST_GROUP_ITEMS && i > groups.back()) groups.push_back(i);
+        groups.push_back(n);
+        for (size_t g = 0; g + 1 < groups.size(); ++g)
+            if (qitems[groups[g + 1]] - qitems[groups[g]] > 0xFFFFFFF0ull) throw Error{KETO_E_RANGE, too_many};
+    }
+    bool one_group() const { return groups.size() == 2; }
+    size_t n_groups() const { return groups.size() - 1; }
+
+    // the count pass of group g; returns its item count.  Afterwards L.items / L.ioff and the count, wave
+    // count and base buffers of the mode describe this group.
+    uint32_t count(size_t g) {
+        const uint32_t g0 = groups[g], g1 = groups[g + 1];
+        const uint32_t m = (uint32_t)(qitems[g1] - qitems[g0]);
+        if (m == 0) return 0;
+        items.resize(m);
+        ioff.resize((uint64_t)(g1 - g0) + 1);
+        for (uint32_t q = g0; q < g1; ++q) {
+            const uint64_t at = qitems[q] - qitems[g0], k = qitems[q + 1] - qitems[q];
+            ioff[q - g0] = (uint32_t)at;
+            for (uint64_t t = 0; t < k; ++t) items[at + t] = LItem{q, (uint32_t)t};
+        }
+        ioff[g1 - g0] = m;
+        LItem* d_items = L.items.get<LItem>(m);
+        uint32_t* d_ioff = L.ioff.get<uint32_t>(ioff.size());
+        uint32_t* d_cnt = L.cnt.get<uint32_t>((uint64_t)m + 1);
+        uint32_t* d_wcnt = L.wcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
+        uint64_t* d_base = L.base.get<uint64_t>((uint64_t)m + 1);
+        HIP_OK(hipMemcpyAsync(d_items, items.data(), (uint64_t)m * sizeof(LItem), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d_ioff, ioff.data(), ioff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (heads) {
+            uint32_t* d_hcnt = L.hcnt.get<uint32_t>((uint64_t)m + 1);
+            uint32_t* d_hwcnt = L.hwcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
+            uint64_t* d_hbase = L.hbase.get<uint64_t>((uint64_t)m + 1);
+            HIP_OK(hipMemsetAsync(d_hcnt + m, 0, sizeof(uint32_t), st));
+            hipLaunchKernelGGL(list_count_heads, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, d_items, tile, d_cnt,
+                               d_wcnt, d_qpoison, d_hcnt, d_hwcnt);
+            HIP_OK(hipGetLastError());
+            scan_counts(L, d_hcnt, d_hbase, m);
+            d_base = d_hbase;
+        } else {
+            HIP_OK(hipMemsetAsync(d_cnt + m, 0, sizeof(uint32_t), st));
+            hipLaunchKernelGGL(list_count, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, d_items, tile, d_cnt, d_wcnt,
+                               d_qpoison);
+            HIP_OK(hipGetLastError());
+            scan_counts(L, d_cnt, d_base, m);
+        }
+        hipLaunchKernelGGL(list_totals, dim3((g1 - g0 + 255) / 256), dim3(256), 0, st, d_base, d_ioff, g0, g1 - g0, d_tot);
+        HIP_OK(hipGetLastError());
+        // several groups share `items` / `ioff`: the copies above must have read them before the next refill
+        if (!one_group()) HIP_OK(hipStreamSynchronize(st));
+        return m;
+    }
+};
+
+}  // namespace
+
+void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, ListResult& out) {
+    if (S.n_parts > 1) throw Error{KETO_E_INVALID, "keto_list_batch: a part of a partitioned snapshot holds only some rows"};
+    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
+    out.status.assign(n, KETO_LIST_OK);
+    out.offsets.assign((uint64_t)n + 1, 0);
+    out.next_page.assign(n, 0);
+    out.totals.assign(n, 0);
+    out.tuples = nullptr;
+    out.index_ms = out.scan_ms = 0;
+    if (n == 0) return;
+    const uint32_t tile = list_tile();
+    std::lock_guard<std::mutex> lk(C.mu);                    // one list call at a time per snapshot
+    ListState& L = current_index(S, C, V.device, out.index_ms);
     hipStream_t st = L.stream;
 
     // ---- resolve (host threads)
@@ -1053,21 +1314,6 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
             out.status[i] = P.status;
         }
     });
-    // items per query, and the query groups of at most LIST_GROUP_ITEMS items (a single query may exceed it)
-    std::vector<uint64_t> qitems((uint64_t)n + 1, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint64_t k = (qs[i].hi - qs[i].lo + tile - 1) / tile;
-        if (k > 0xFFFFFFF0ull) throw Error{KETO_E_RANGE, "keto_list_batch: a query spans more than 2^32 tiles"};
-        qitems[i + 1] = qitems[i] + k;
-    }
-    std::vector<uint32_t> groups{0};
-    for (uint32_t i = 0; i < n; ++i)
-        if (qitems[i + 1] - qitems[groups.back()] > LIST_GROUP_ITEMS && i > groups.back()) groups.push_back(i);
-    groups.push_back(n);
-    for (size_t g = 0; g + 1 < groups.size(); ++g)
-        if (qitems[groups[g + 1]] - qitems[groups[g]] > 0xFFFFFFF0ull)
-            throw Error{KETO_E_RANGE, "keto_list_batch: a query spans more than 2^32 tiles"};
-
     LQuery* d_qs = L.qs.get<LQuery>(n);
     uint64_t* d_tot = L.tot.get<uint64_t>(n);
     uint32_t* d_qpoison = L.qpoison.get<uint32_t>(n);
@@ -1088,49 +1334,10 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
     HIP_OK(hipMemsetAsync(d_qpoison, 0, (uint64_t)n * sizeof(uint32_t), st));
     HIP_OK(hipMemsetAsync(d_qpage, 0, (uint64_t)n * sizeof(uint32_t), st));
 
-    // the count pass of one query group: its items, their counts, the scanned bases and the totals;
-    // returns the group's item count (the buffers hold one group at a time)
-    std::vector<LItem> items;
-    std::vector<uint32_t> ioff;
-    const bool one_group = groups.size() == 2;
-    auto count_group = [&](uint32_t g0, uint32_t g1) -> uint32_t {
-        const uint32_t m = (uint32_t)(qitems[g1] - qitems[g0]);
-        if (m == 0) return 0;
-        items.resize(m);
-        ioff.resize((uint64_t)(g1 - g0) + 1);
-        for (uint32_t q = g0; q < g1; ++q) {
-            const uint64_t at = qitems[q] - qitems[g0], k = qitems[q + 1] - qitems[q];
-            ioff[q - g0] = (uint32_t)at;
-            for (uint64_t t = 0; t < k; ++t) items[at + t] = LItem{q, (uint32_t)t};
-        }
-        ioff[g1 - g0] = m;
-        LItem* d_items = L.items.get<LItem>(m);
-        uint32_t* d_ioff = L.ioff.get<uint32_t>(ioff.size());
-        uint32_t* d_cnt = L.cnt.get<uint32_t>((uint64_t)m + 1);
-        uint32_t* d_wcnt = L.wcnt.get<uint32_t>((uint64_t)m * LIST_WAVES);
-        uint64_t* d_base = L.base.get<uint64_t>((uint64_t)m + 1);
-        HIP_OK(hipMemcpyAsync(d_items, items.data(), (uint64_t)m * sizeof(LItem), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(d_ioff, ioff.data(), ioff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemsetAsync(d_cnt + m, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(list_count, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, d_items, tile, d_cnt, d_wcnt,
-                           d_qpoison);
-        HIP_OK(hipGetLastError());
-        struct Widen {
-            __host__ __device__ uint64_t operator()(uint32_t c) const { return c; }
-        };
-        hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*> cit(d_cnt, Widen{});
-        size_t tb = 0;
-        HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cit, d_base, (uint64_t)m + 1, st));
-        void* tmp = L.tmp.get<uint8_t>(tb);
-        HIP_OK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cit, d_base, (uint64_t)m + 1, st));
-        hipLaunchKernelGGL(list_totals, dim3((g1 - g0 + 255) / 256), dim3(256), 0, st, d_base, d_ioff, g0, g1 - g0, d_tot);
-        HIP_OK(hipGetLastError());
-        // several groups share `items` / `ioff`: the copies above must have read them before the next refill
-        if (!one_group) HIP_OK(hipStreamSynchronize(st));
-        return m;
-    };
+    // the count pass, group by group (the buffers hold one group at a time)
+    GroupedCount G(L, tile, /*heads=*/false, qs, d_qs, d_tot, d_qpoison, "keto_list_batch");
     uint32_t m_last = 0;
-    for (size_t g = 0; g + 1 < groups.size(); ++g) m_last = count_group(groups[g], groups[g + 1]);
+    for (size_t g = 0; g < G.n_groups(); ++g) m_last = G.count(g);
 
     // ---- the one host sync between the passes: totals -> sizes, statuses, tokens
     std::vector<uint64_t> tot(n);
@@ -1166,12 +1373,12 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
         LWindow* d_wins = L.wins.get<LWindow>(n);
         uint2* d_out = L.out.get<uint2>(total_out);
         HIP_OK(hipMemcpyAsync(d_wins, wins.data(), (uint64_t)n * sizeof(LWindow), hipMemcpyHostToDevice, st));
-        for (size_t g = 0; g + 1 < groups.size(); ++g) {
-            const uint32_t m = one_group ? m_last : count_group(groups[g], groups[g + 1]);
+        for (size_t g = 0; g < G.n_groups(); ++g) {
+            const uint32_t m = G.one_group() ? m_last : G.count(g);
             if (m == 0) continue;
             hipLaunchKernelGGL(list_emit, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, (const LItem*)L.items.p, tile,
                                (const uint32_t*)L.cnt.p, (const uint32_t*)L.wcnt.p, (const uint64_t*)L.base.p,
-                               (const uint32_t*)L.ioff.p, groups[g], d_wins, d_out, total_out, d_qpage);
+                               (const uint32_t*)L.ioff.p, G.groups[g], d_wins, d_out, total_out, d_qpage);
             HIP_OK(hipGetLastError());
         }
         block.p = pinned_take(total_out * sizeof(keto_list_tuple));
@@ -1472,6 +1679,224 @@ bool delete_index_patch(const Snapshot& S, ListCache& C, const DeleteScan& sc) n
         }
         return false;
     }
+}
+
+// ---- keto_lookup_objects_batch: which objects of a namespace does a subject have a relation on
+namespace {
+
+uint64_t lookup_env(const char* name, uint64_t def, uint64_t lo, uint64_t hi) {
+    const char* e = getenv(name);
+    if (!e) return def;
+    const long long v = atoll(e);
+    if (v < (long long)lo || (uint64_t)v > hi)
+        throw Error{KETO_E_INVALID, std::string(name) + " must lie in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]"};
+    return (uint64_t)v;
+}
+
+}  // namespace
+
+void lookup_objects(Snapshot& S, ListCache& C, const keto_lookup_req* reqs, uint32_t n, int32_t gmd, LookupResult& out) {
+    if (S.n_parts > 1)
+        throw Error{KETO_E_INVALID, "keto_lookup_objects_batch: a part of a partitioned snapshot holds only some rows"};
+    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
+    out.status.assign(n, KETO_LOOKUP_OK);
+    out.offsets.assign((uint64_t)n + 1, 0);
+    out.next_page.assign(n, 0);
+    out.totals.assign(n, 0);
+    out.candidates.assign(n, 0);
+    out.undecided.assign(n, 0);
+    out.rows = nullptr;
+    out.index_ms = out.candidates_ms = out.check_ms = out.emit_ms = 0;
+    if (n == 0) return;
+    const uint32_t tile = list_tile();
+    const uint64_t chunk = lookup_env("KETO_LOOKUP_CHUNK", 1ull << 22, 64, 1ull << 30);
+    const uint64_t max_cand = lookup_env("KETO_LOOKUP_MAX_CANDIDATES", 1ull << 28, 0, 1ull << 40);
+    std::lock_guard<std::mutex> lk(C.mu);                    // one list or lookup call at a time per snapshot
+    ListState& L = current_index(S, C, V.device, out.index_ms);
+    hipStream_t st = L.stream;
+    struct Trim {
+        ListState& l;
+        ~Trim() { l.lookup_trim(); }
+    } trim{L};
+
+    // ---- plan (host): namespace + relation through the list resolver, the subject as a check target
+    std::vector<LQuery> qs(n);
+    std::vector<LSubj> subj(n);
+    const unsigned th = n >= 4096 ? build_threads() : 1u;
+    par_chunks(n, th, 1024, [&](uint64_t pb, uint64_t pe, unsigned) {
+        for (uint64_t i = pb; i < pe; ++i) {
+            const keto_lookup_req& rq = reqs[i];
+            qs[i] = LQuery{0, 0, ANY, ANY, ANY, 0};
+            subj[i] = LSubj{KETO_NO_TARGET, 0, rq.max_depth, 0};
+            const keto_subject& sb = rq.subject;
+            if (!rq.namespace_.n || !rq.relation.n ||
+                (sb.kind != 0 && (!sb.set_namespace.n || !sb.set_object.n || !sb.set_relation.n))) {
+                out.status[i] = KETO_LOOKUP_UNSUPPORTED;
+                continue;
+            }
+            keto_list_req lr;
+            std::memset(&lr, 0, sizeof lr);
+            lr.namespace_ = rq.namespace_;
+            lr.relation = rq.relation;
+            const Plan P = resolve_list(S, L, lr);
+            if (P.status != KETO_LIST_OK) {
+                out.status[i] = KETO_LOOKUP_UNKNOWN_NAMESPACE;
+                continue;
+            }
+            qs[i] = P.q;
+            if (sb.kind == 0) {
+                const int64_t sid = S.lookup_str(sv(sb.id));
+                if (sid >= 0) subj[i].target = (uint32_t)sid;
+            } else {
+                const int64_t t = S.resolve_query(sv(sb.set_namespace), sv(sb.set_object), sv(sb.set_relation));
+                if (t >= 0) {
+                    subj[i].target = (uint32_t)t;
+                    subj[i].flags = 1;
+                }
+            }
+        }
+    });
+
+    // ---- candidates: the HEAD passes over all queries, in query groups as in list_batch
+    LQuery* d_qs = L.qs.get<LQuery>(n);
+    uint64_t* d_tot = L.tot.get<uint64_t>(n);
+    uint32_t* d_qpoison = L.qpoison.get<uint32_t>(n);        // written by the HEAD count, never read here
+    for (hipEvent_t& x : L.lk_ev)                            // made once, kept with the index state
+        if (!x) HIP_OK(hipEventCreate(&x));
+    hipEvent_t* const ev = L.lk_ev;
+    HIP_OK(hipEventRecord(ev[0], st));
+    HIP_OK(hipMemcpyAsync(d_qs, qs.data(), (uint64_t)n * sizeof(LQuery), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_tot, 0, (uint64_t)n * sizeof(uint64_t), st));
+    HIP_OK(hipMemsetAsync(d_qpoison, 0, (uint64_t)n * sizeof(uint32_t), st));
+    GroupedCount G(L, tile, /*heads=*/true, qs, d_qs, d_tot, d_qpoison, "keto_lookup_objects_batch");
+    uint32_t m_last = 0;
+    for (size_t g = 0; g < G.n_groups(); ++g) m_last = G.count(g);
+
+    // ---- the first host sync: candidates per query -> qoff, the cap, the buffers' sizes
+    std::vector<uint64_t> qoff((uint64_t)n + 1, 0);
+    HIP_OK(hipMemcpyAsync(out.candidates.data(), d_tot, (uint64_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < n; ++i) qoff[i + 1] = qoff[i] + out.candidates[i];
+    const uint64_t H = qoff[n];
+    if (H > max_cand)
+        throw Error{KETO_E_INVALID, "keto_lookup_objects_batch: " + std::to_string(H) + " candidates, more than KETO_LOOKUP_MAX_CANDIDATES (" +
+                                        std::to_string(max_cand) + ")"};
+    if (H == 0) {
+        HIP_OK(hipEventRecord(ev[1], st));
+        HIP_OK(hipStreamSynchronize(st));
+        HIP_OK(hipEventElapsedTime(&out.candidates_ms, ev[0], ev[1]));
+        return;                                              // every total is 0
+    }
+    uint32_t* d_cand = L.lk_cand.get<uint32_t>(H);
+    uint64_t* d_qoff = L.lk_qoff.get<uint64_t>((uint64_t)n + 1);
+    LSubj* d_subj = L.lk_subj.get<LSubj>(n);
+    std::vector<LWindow> wins(n);
+    for (uint32_t i = 0; i < n; ++i) wins[i] = LWindow{0, out.candidates[i], qoff[i]};
+    LWindow* d_wins = L.wins.get<LWindow>(n);
+    HIP_OK(hipMemcpyAsync(d_wins, wins.data(), (uint64_t)n * sizeof(LWindow), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_qoff, qoff.data(), ((uint64_t)n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_subj, subj.data(), (uint64_t)n * sizeof(LSubj), hipMemcpyHostToDevice, st));
+    for (size_t g = 0; g < G.n_groups(); ++g) {
+        const uint32_t m = G.one_group() ? m_last : G.count(g);
+        if (m == 0) continue;
+        hipLaunchKernelGGL(list_emit_heads, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, (const LItem*)L.items.p, tile,
+                           (const uint32_t*)L.hcnt.p, (const uint32_t*)L.hwcnt.p, (const uint64_t*)L.hbase.p,
+                           (const uint32_t*)L.ioff.p, G.groups[g], d_wins, reinterpret_cast<uint2*>(d_cand), H, nullptr);
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipEventRecord(ev[1], st));
+
+    // ---- check, in chunks: requests made on the device, decisions written straight into dec[]
+    const uint64_t dec_bytes = (H + 7) & ~3ull;             // padded: lookup_quad loads whole words
+    uint8_t* d_dec = L.lk_dec.get<uint8_t>(dec_bytes);
+    uint4* d_reqs = L.lk_reqs.get<uint4>(std::min(chunk, H));
+    HIP_OK(hipMemsetAsync(d_dec + (H & ~3ull), 0, dec_bytes - (H & ~3ull), st));
+    for (uint64_t c0 = 0; c0 < H; c0 += chunk) {
+        const uint32_t m = (uint32_t)std::min(chunk, H - c0);
+        hipLaunchKernelGGL(lookup_make_reqs, dim3((m + LIST_THREADS - 1) / LIST_THREADS), dim3(LIST_THREADS), 0, st,
+                           (const uint32_t*)d_cand, (const uint64_t*)d_qoff, n, (const LSubj*)d_subj, c0, m, d_reqs);
+        HIP_OK(hipGetLastError());
+        device_check_rows(S, reinterpret_cast<const keto_check_ids*>(d_reqs), m, gmd, d_dec + c0, st, /*rows_valid=*/true);
+    }
+    HIP_OK(hipEventRecord(ev[2], st));
+
+    // ---- ordered compaction: items over the queries' candidates, count / scan / emit
+    std::vector<uint64_t> citems((uint64_t)n + 1, 0);
+    for (uint32_t i = 0; i < n; ++i) citems[i + 1] = citems[i] + (out.candidates[i] + tile - 1) / tile;
+    if (citems[n] > 0x7FFFFFF0ull) throw Error{KETO_E_RANGE, "keto_lookup_objects_batch: more than 2^31 candidate tiles"};
+    const uint32_t cm = (uint32_t)citems[n];
+    std::vector<LItem> cit(cm);
+    std::vector<uint32_t> cioff((uint64_t)n + 1);
+    for (uint32_t q = 0; q < n; ++q) {
+        cioff[q] = (uint32_t)citems[q];
+        for (uint64_t t = 0; t < citems[q + 1] - citems[q]; ++t) cit[citems[q] + t] = LItem{q, (uint32_t)t};
+    }
+    cioff[n] = cm;
+    LItem* d_items = L.items.get<LItem>(cm);
+    uint32_t* d_ioff = L.ioff.get<uint32_t>((uint64_t)n + 1);
+    uint32_t* d_cnt = L.cnt.get<uint32_t>((uint64_t)cm + 1);
+    uint32_t* d_wcnt = L.wcnt.get<uint32_t>((uint64_t)cm * LIST_WAVES);
+    uint64_t* d_base = L.base.get<uint64_t>((uint64_t)cm + 1);
+    unsigned long long* d_und = L.lk_und.get<unsigned long long>(n);
+    HIP_OK(hipMemcpyAsync(d_items, cit.data(), (uint64_t)cm * sizeof(LItem), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_ioff, cioff.data(), ((uint64_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_cnt + cm, 0, sizeof(uint32_t), st));
+    HIP_OK(hipMemsetAsync(d_und, 0, (uint64_t)n * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(lookup_count, dim3(cm), dim3(LIST_THREADS), 0, st, (const uint8_t*)d_dec, (const uint64_t*)d_qoff,
+                       (const LItem*)d_items, tile, d_cnt, d_wcnt, d_und);
+    HIP_OK(hipGetLastError());
+    scan_counts(L, d_cnt, d_base, cm);
+    hipLaunchKernelGGL(list_totals, dim3((n + 255) / 256), dim3(256), 0, st, d_base, d_ioff, 0u, n, d_tot);
+    HIP_OK(hipGetLastError());
+
+    // ---- the second host sync: totals -> statuses, tokens, windows, the pinned block's size
+    std::vector<uint64_t> tot(n);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the undecided counters are 64-bit");
+    HIP_OK(hipMemcpyAsync(tot.data(), d_tot, (uint64_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(out.undecided.data(), d_und, (uint64_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t total_out = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        wins[i] = LWindow{0, 0, total_out};
+        out.offsets[i] = total_out;
+        if (out.status[i] != KETO_LOOKUP_OK) continue;
+        if (out.undecided[i]) {
+            out.status[i] = KETO_LOOKUP_UNDECIDED;
+            continue;
+        }
+        const uint64_t size = reqs[i].page_size ? reqs[i].page_size : S.page_size;
+        const uint64_t page = std::max<uint32_t>(reqs[i].page, 1u);
+        const uint64_t first = (page - 1) * size;                       // < 2^63
+        const uint64_t k = tot[i] > first ? std::min(size, tot[i] - first) : 0;
+        out.totals[i] = tot[i];
+        out.next_page[i] = page >= (tot[i] + size - 1) / size ? 0 : page + 1;
+        wins[i].wlo = first;
+        wins[i].whi = first + k;
+        total_out += k;
+    }
+    out.offsets[n] = total_out;
+    struct Block {                                          // the result's pinned block until it is handed over
+        void* p = nullptr;
+        ~Block() { pinned_give(p); }
+    } block;
+    if (total_out) {
+        uint32_t* d_out = L.out.get<uint32_t>(total_out);
+        HIP_OK(hipMemcpyAsync(d_wins, wins.data(), (uint64_t)n * sizeof(LWindow), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(lookup_emit, dim3(cm), dim3(LIST_THREADS), 0, st, (const uint8_t*)d_dec, (const uint32_t*)d_cand,
+                           (const uint64_t*)d_qoff, (const LItem*)d_items, tile, (const uint32_t*)d_cnt,
+                           (const uint32_t*)d_wcnt, (const uint64_t*)d_base, (const uint32_t*)d_ioff,
+                           (const LWindow*)d_wins, d_out, total_out);
+        HIP_OK(hipGetLastError());
+        block.p = pinned_take(total_out * sizeof(uint32_t));
+        HIP_OK(hipMemcpyAsync(block.p, d_out, total_out * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipEventRecord(ev[3], st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipEventElapsedTime(&out.candidates_ms, ev[0], ev[1]));
+    HIP_OK(hipEventElapsedTime(&out.check_ms, ev[1], ev[2]));
+    HIP_OK(hipEventElapsedTime(&out.emit_ms, ev[2], ev[3]));
+    out.rows = static_cast<uint32_t*>(block.p);
+    block.p = nullptr;
 }
 
 }  // namespace keto

@@ -35,6 +35,21 @@ void list_plan(const Snapshot& s, ListCache& c, const keto_list_req* reqs, uint3
 void list_batch(Snapshot& s, ListCache& c, const keto_list_req* reqs, uint32_t n, ListResult& out);
 uint64_t list_device_bytes(ListCache& c);   // device memory of the list index (0 before the first list_batch)
 
+// keto_lookup_objects_batch (list.hip): per query the tuple rows (namespace, o, relation), in key
+// order, whose check against the query's subject is allowed; the page of them
+struct LookupResult {
+    std::vector<uint8_t> status;                        // n x KETO_LOOKUP_*
+    std::vector<uint64_t> offsets, next_page, totals;   // n + 1, n, n
+    std::vector<uint64_t> candidates, undecided;        // n, n
+    uint32_t* rows = nullptr;                           // a block of the pinned pool (pinned_take), or NULL
+    float index_ms = 0, candidates_ms = 0, check_ms = 0, emit_ms = 0;
+};
+// The caller holds the snapshot's lock shared, from before the call until it returns: the candidates,
+// their checks and the page belong to one version.  Holds c.mu throughout, and the device lock
+// (device_check_rows) inside it per chunk.  out.rows goes to the caller, who gives it back with pinned_give.
+void lookup_objects(Snapshot& s, ListCache& c, const keto_lookup_req* reqs, uint32_t n, int32_t global_max_depth,
+                    LookupResult& out);
+
 // The journal of written rows.  keto_snapshot_apply, holding the snapshot's lock exclusive, after the
 // commit that took the version from ver_before to ver_after: notes the rows it changed.  Nothing is
 // noted without index state; past KETO_LIST_PATCH_MAX_ROWS distinct rows, with KETO_LIST_PATCH=0, or when
