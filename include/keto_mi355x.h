@@ -843,6 +843,96 @@ const uint64_t* keto_looked_undecided(const keto_looked*);  /* of them: checks t
  * chunks' requests and checks, emit_ms = the count, scan and emit of the allowed rows and their copy */
 int keto_looked_timing(const keto_looked*, float* index_ms, float* candidates_ms, float* check_ms, float* emit_ms);
 
+/* ---- Subjects of an object: Expand flattened on the device (repo:keto_amd/csrc/subjects.hip) ----
+ * keto_subjects_batch answers, per query, "which subjects have `relation` on `namespace_`:`object`".
+ * Keto v0.8.1 has no call for it: a caller expands the subject set and flattens the tree.  This call
+ * does exactly that, on the device.  Let T be the tree keto_expand_batch returns for the subject set
+ * namespace_:object#relation at the request's max_depth, clamped as BuildTree clamps it
+ * (internal/expand/engine.go:35-37).  Query i answers with the DISTINCT SubjectID LEAVES OF T, each as
+ * its string id (the keto_tree_node.subject word, bit 31 clear; decode with
+ * keto_subject_fields(s, NULL, ...)), in ASCENDING STRING-ID ORDER; the page is ids
+ * [(page-1) * size, page * size) of them with page = max(page, 1), page_size 0 = the snapshot's page
+ * size; next_page and the total follow the list rule (above), the total being the number of distinct
+ * SubjectID leaves.
+ *
+ * The order is the string id's, not the bytes'.  String ids are in byte order for every string present
+ * when the snapshot was built; strings added by keto_snapshot_apply are appended and no id ever moves
+ * (see the list section).  So a subject first written after the build sorts behind every older one
+ * whatever its bytes, and a page token stays meaningful across writes: the ids before a page only
+ * change when a subject of the set itself comes or goes.  Byte order would need a rank table over all
+ * strings per version.
+ *
+ * This is Expand's answer with Expand's quirks -- one visited map per tree, the depth cut at
+ * restDepth <= 1, nil children turned into leaves -- NOT "every subject for which a check is allowed".
+ * The two agree when the depth is ample and no subject set is visited twice on different paths; they
+ * can differ otherwise.  There is no check-semantics variant.  Per query the call reports what tells
+ * the caller so: `leaves` = the SubjectID leaf nodes of T before deduplication, `set_leaves` = the leaf
+ * nodes of T whose subject is a subject set (depth-cut, revisited or empty sets; a node count, not a
+ * distinct count).  set_leaves != 0: the list may be cut short by the depth.  Subject-set leaves are
+ * not returned as subjects (they may name batch-local wildcard rows only an arena can decode): a caller
+ * who needs them asks keto_expand_batch.
+ *
+ * A query with an empty field is a wildcard root and goes through the batch's overlay exactly as in
+ * keto_expand_batch; its id leaves are ordinary string ids.  KETO_SUBJECTS_NOT_FOUND is
+ * KETO_EXPAND_NOT_FOUND (unknown namespace), KETO_SUBJECTS_UNDECIDED is KETO_EXPAND_UNDECIDED (no ids,
+ * total 0: ask the reference); a nil tree is KETO_SUBJECTS_OK with total 0 and set_leaves 0.
+ *
+ * On the device: the expand leaves its node arena in the snapshot's buffers (as for
+ * keto_expand_encode_batch); a 64-bit scan over the id-leaf flags and a compaction give each tree its
+ * segment of leaf words; a segment is sorted and made distinct by one of three kernels chosen by its
+ * length L: L <= 64 a wave (bitonic network over the lanes), L <= KETO_SUBJECTS_LDS (environment,
+ * default 2048; a power of two in [128, 8192], anything else fails the call with KETO_E_INVALID) a
+ * block sorting in LDS, longer ones one radix sort over 64-bit (segment, word) keys and a streaming
+ * unique; one kernel copies the windows, one DMA brings the page back.  Device memory, derived, not
+ * measured: 8 B of scan and 4 B of leaf words per NODE of the arena (the leaf buffer is sized for the
+ * bound, every node; 4 B per id leaf are used), 8 B twice per id leaf of the radix-sorted class (the
+ * sort is out of place), 64 B per query (segment start, three counts, class lists, window), 4 B per
+ * emitted id; each buffer is kept for the next call up to 256 MB and freed at the end of the call past
+ * that (not counted in keto_snapshot_stats.device_bytes).  More than 2^31 - 1 leaves in the
+ * radix-sorted class fail the call with KETO_E_RANGE.
+ *
+ * The result owns a block of the pinned pool sized exactly after the totals (a huge page_size
+ * allocates nothing) and holds no reference to the snapshot: it stays readable after
+ * keto_snapshot_apply and keto_snapshot_release, until keto_subjects_free.  Errors, as for
+ * keto_expand_encode_batch: NULL arguments are KETO_E_INVALID, checked first; a host-only snapshot is
+ * KETO_E_HIP whatever n is; a migrating part (KETO_PART_MIGRATE, n_parts > 1) and a root owned by
+ * another shared-rows part are KETO_E_INVALID; n = 0 gives count 0 and offsets {0}.  The call takes
+ * the snapshot's lock shared from the expand to the page, the device state's mutex for the expand and
+ * the passes over its arena, and runs one flatten at a time per snapshot. */
+#define KETO_SUBJECTS_OK 0          /* ids, next_page, total = the distinct SubjectID leaves of the expand tree */
+#define KETO_SUBJECTS_NOT_FOUND 1   /* KETO_EXPAND_NOT_FOUND: unknown namespace; no ids, total 0 */
+#define KETO_SUBJECTS_UNDECIDED 2   /* KETO_EXPAND_UNDECIDED: the tree exceeded the engine's limits; no ids, total 0 */
+typedef struct {
+    keto_str namespace_, object, relation;  /* the subject set to expand; an empty field = a wildcard root */
+    int32_t  max_depth;                     /* <= 0 or > global -> global, as keto_expand_req */
+    uint32_t page_size;                     /* 0 -> the snapshot's page_size */
+    uint32_t page;                          /* 0 = page 1 */
+} keto_subjects_req;
+typedef struct keto_subjects keto_subjects;
+int keto_subjects_batch(keto_snapshot* s, const keto_subjects_req* reqs, uint32_t n, int32_t global_max_depth,
+                        keto_subjects** out);
+/* Same with pre-resolved roots, as keto_expand_batch_ids takes them; page_size and page hold n entries
+ * each.  Every root must have bit 31 set (a subject set's row): one without fails the call with
+ * KETO_E_INVALID before *out is touched. */
+int keto_subjects_batch_ids(keto_snapshot* s, const uint32_t* roots, const int32_t* max_depth,
+                            const uint32_t* page_size, const uint32_t* page, uint32_t n, int32_t global_max_depth,
+                            keto_subjects** out);
+void keto_subjects_free(keto_subjects*);                        /* NULL is fine */
+uint32_t        keto_subjects_count(const keto_subjects*);      /* n */
+const uint32_t* keto_subjects_ids(const keto_subjects*, uint64_t* total_out);  /* string ids (NULL when there are none) */
+const uint64_t* keto_subjects_offsets(const keto_subjects*);    /* n+1; query i = ids[off[i], off[i+1]) */
+const uint8_t*  keto_subjects_status(const keto_subjects*);     /* n x KETO_SUBJECTS_* */
+const uint64_t* keto_subjects_next_page(const keto_subjects*);  /* the list rule: 0 on the last page, when there is nothing, or past the end */
+const uint64_t* keto_subjects_totals(const keto_subjects*);     /* distinct SubjectID leaves of the whole tree */
+const uint64_t* keto_subjects_leaves(const keto_subjects*);     /* SubjectID leaf nodes before deduplication */
+const uint64_t* keto_subjects_set_leaves(const keto_subjects*); /* leaf nodes whose subject is a subject set */
+/* of the call that made the result: expand_ms = the expand half (host wall time, as a caller pays it),
+ * flatten_ms = everything after it on the flatten's stream (HIP events) */
+int keto_subjects_timing(const keto_subjects*, float* expand_ms, float* flatten_ms);
+/* five HIP-event times in ms: the scan and compaction, the wave class, the block class, the radix-sorted
+ * class, the counts' copy + windows + emit + the page's DMA (NULL for a NULL result) */
+const float* keto_subjects_stages(const keto_subjects*);
+
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,
  * internal/relationtuple/definitions.go:40-42,102-117) straight from the node arena without a text

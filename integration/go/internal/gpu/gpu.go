@@ -937,3 +937,96 @@ func (s *Snapshot) LookupObjects(qs []LookupQuery, globalMax int) ([]LookupResul
 	}
 	return out, nil
 }
+
+// Subjects statuses of Subjects (KETO_SUBJECTS_*).
+const (
+	SubjectsOK        = uint8(C.KETO_SUBJECTS_OK)
+	SubjectsNotFound  = uint8(C.KETO_SUBJECTS_NOT_FOUND) // herodot.ErrNotFound: unknown namespace
+	SubjectsUndecided = uint8(C.KETO_SUBJECTS_UNDECIDED) // the tree exceeded the engine's limits: expand it with the reference engine
+)
+
+// SubjectsQuery asks which subject ids have Relation on Namespace:Object (keto_subjects_req): the subject
+// set that is expanded.  An empty field makes a wildcard root, as for Expand.  MaxDepth <= 0 or past the
+// global maximum is the global maximum; PageSize 0 is the snapshot's page size and Page 0 the first page.
+type SubjectsQuery struct {
+	Namespace, Object, Relation string
+	MaxDepth                    int
+	PageSize, Page              uint32
+}
+
+// SubjectsResult is one query's page of subject ids in ascending string-id order (byte order for the
+// strings of the build, strings written later behind them), the next page's number (0: the last page), the
+// count of all distinct subject ids of the tree, its SubjectID leaf nodes before deduplication, and its
+// leaf nodes that are subject sets (depth-cut, revisited or empty sets: not returned; non-zero means the
+// list may be cut short by the depth).
+type SubjectsResult struct {
+	Status    uint8
+	IDs       []string
+	NextPage  uint64
+	Total     uint64
+	Leaves    uint64
+	SetLeaves uint64
+}
+
+// Subjects answers, for many subject sets, which subject ids Expand finds under them
+// (keto_subjects_batch): the distinct SubjectID leaves of the tree expand.(*Engine).BuildTree
+// (internal/expand/engine.go:32-102) returns, flattened on the device.  It is Expand's answer, with its
+// depth cut and its one visited map per tree, not a check per subject.  The ids come back as string
+// ids; their strings are read with keto_subject_fields, one call for the batch.  Not for a migrating
+// Partition (KETO_E_INVALID).
+func (s *Snapshot) Subjects(qs []SubjectsQuery, globalMax int) ([]SubjectsResult, error) {
+	n := len(qs)
+	if n == 0 {
+		return nil, nil
+	}
+	var m cmem
+	defer m.free()
+	total := 0
+	for i := range qs {
+		total += len(qs[i].Namespace) + len(qs[i].Object) + len(qs[i].Relation)
+	}
+	m.strings(total)
+	cr := (*C.keto_subjects_req)(m.alloc(n * int(C.sizeof_keto_subjects_req)))
+	cs := unsafe.Slice(cr, n)
+	for i := range qs {
+		q := &qs[i]
+		cs[i] = C.keto_subjects_req{namespace_: m.s(q.Namespace), object: m.s(q.Object), relation: m.s(q.Relation),
+			max_depth: C.int32_t(q.MaxDepth), page_size: C.uint32_t(q.PageSize), page: C.uint32_t(q.Page)}
+	}
+	var r *C.keto_subjects
+	if rc := C.keto_subjects_batch(s.h, cr, C.uint32_t(n), C.int32_t(globalMax), &r); rc != C.KETO_OK {
+		return nil, lastErr(rc)
+	}
+	defer C.keto_subjects_free(r)
+	var count C.uint64_t
+	ip := C.keto_subjects_ids(r, &count)
+	off := unsafe.Slice(C.keto_subjects_offsets(r), n+1)
+	status := unsafe.Slice(C.keto_subjects_status(r), n)
+	next := unsafe.Slice(C.keto_subjects_next_page(r), n)
+	totals := unsafe.Slice(C.keto_subjects_totals(r), n)
+	leaves := unsafe.Slice(C.keto_subjects_leaves(r), n)
+	sets := unsafe.Slice(C.keto_subjects_set_leaves(r), n)
+	var refs []uint32
+	if ip != nil && count > 0 {
+		ids := unsafe.Slice(ip, int(count)) // the result's memory: read before keto_subjects_free
+		refs = make([]uint32, len(ids))
+		for i, id := range ids {
+			refs[i] = uint32(id)
+		}
+	}
+	subjects, err := s.subjects(nil, refs, &m)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]SubjectsResult, n)
+	for i := 0; i < n; i++ {
+		out[i] = SubjectsResult{Status: uint8(status[i]), NextPage: uint64(next[i]), Total: uint64(totals[i]),
+			Leaves: uint64(leaves[i]), SetLeaves: uint64(sets[i])}
+		page := subjects[int(off[i]):int(off[i+1])]
+		out[i].IDs = make([]string, len(page))
+		for k, sub := range page {
+			out[i].IDs[k] = sub.(*relationtuple.SubjectID).ID
+		}
+	}
+	return out, nil
+}

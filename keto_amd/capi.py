@@ -50,10 +50,14 @@ EXPORTS = [
     "keto_lookup_objects_batch", "keto_looked_free", "keto_looked_count", "keto_looked_rows", "keto_looked_offsets",
     "keto_looked_status", "keto_looked_next_page", "keto_looked_totals", "keto_looked_candidates",
     "keto_looked_undecided", "keto_looked_timing",
+    "keto_subjects_batch", "keto_subjects_batch_ids", "keto_subjects_free", "keto_subjects_count", "keto_subjects_ids",
+    "keto_subjects_offsets", "keto_subjects_status", "keto_subjects_next_page", "keto_subjects_totals",
+    "keto_subjects_leaves", "keto_subjects_set_leaves", "keto_subjects_timing", "keto_subjects_stages",
 ]
 DELETE_PATH_HOST, DELETE_PATH_DEVICE = 0, 1
 LIST_OK, LIST_NOT_FOUND, LIST_UNDECIDED = 0, 1, 2
 LOOKUP_OK, LOOKUP_UNKNOWN_NAMESPACE, LOOKUP_UNDECIDED, LOOKUP_UNSUPPORTED = 0, 1, 2, 3
+SUBJECTS_OK, SUBJECTS_NOT_FOUND, SUBJECTS_UNDECIDED = 0, 1, 2
 ENC_PROTO, ENC_JSON = 0, 1
 ENCODINGS = {"proto": ENC_PROTO, "json": ENC_JSON}
 PART_SHARED, PART_MIGRATE = 0, 1
@@ -141,6 +145,11 @@ class KListReq(C.Structure):
 
 class KLookupReq(C.Structure):
     _fields_ = [("namespace_", KStr), ("relation", KStr), ("subject", KSubject), ("max_depth", C.c_int32),
+                ("page_size", C.c_uint32), ("page", C.c_uint32)]
+
+
+class KSubjectsReq(C.Structure):
+    _fields_ = [("namespace_", KStr), ("object", KStr), ("relation", KStr), ("max_depth", C.c_int32),
                 ("page_size", C.c_uint32), ("page", C.c_uint32)]
 
 
@@ -277,6 +286,18 @@ def load():
             f.restype = C.c_void_p
             f.argtypes = [C.c_void_p]
         lib.keto_looked_timing.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 4
+    if hasattr(lib, "keto_subjects_batch"):
+        lib.keto_subjects_free.restype = None
+        lib.keto_subjects_free.argtypes = [C.c_void_p]
+        lib.keto_subjects_count.restype = C.c_uint32
+        lib.keto_subjects_count.argtypes = [C.c_void_p]
+        lib.keto_subjects_ids.restype = C.c_void_p
+        lib.keto_subjects_ids.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        for f in (lib.keto_subjects_offsets, lib.keto_subjects_status, lib.keto_subjects_next_page, lib.keto_subjects_totals,
+                  lib.keto_subjects_leaves, lib.keto_subjects_set_leaves, lib.keto_subjects_stages):
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p]
+        lib.keto_subjects_timing.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 2
     lib.keto_route_work_bytes.argtypes = [C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
@@ -985,6 +1006,86 @@ class Snapshot:
         return [(int(r["status"][i]), objs[int(offs[i]):int(offs[i + 1])],
                  str(int(r["next_page"][i])) if r["next_page"][i] else "", int(r["totals"][i]),
                  int(r["candidates"][i]), int(r["undecided"][i])) for i in range(len(queries))]
+
+    # ------------------------------------------------------------------ subjects of an object
+    def _subjects_arrays(self, h):
+        """The arrays of a keto_subjects handle, copied out (the handle stays the caller's)."""
+        n = self.lib.keto_subjects_count(h)
+        total = C.c_uint64()
+        p = self.lib.keto_subjects_ids(h, C.byref(total))
+        get = lambda f, nbytes, dt: np.frombuffer(C.string_at(f(h), nbytes), dtype=dt).copy()
+        out = {"status": get(self.lib.keto_subjects_status, n, np.uint8),
+               "offsets": get(self.lib.keto_subjects_offsets, 8 * (n + 1), np.uint64),
+               "next_page": get(self.lib.keto_subjects_next_page, 8 * n, np.uint64),
+               "totals": get(self.lib.keto_subjects_totals, 8 * n, np.uint64),
+               "leaves": get(self.lib.keto_subjects_leaves, 8 * n, np.uint64),
+               "set_leaves": get(self.lib.keto_subjects_set_leaves, 8 * n, np.uint64),
+               "ids": (np.frombuffer(C.string_at(p, 4 * total.value), dtype=np.uint32).copy() if total.value
+                       else np.zeros(0, dtype=np.uint32)),
+               "stages": tuple(get(self.lib.keto_subjects_stages, 4 * 5, np.float32).tolist())}
+        ms = [C.c_float() for _ in range(2)]
+        _check(self.lib.keto_subjects_timing(h, *[C.byref(x) for x in ms]))
+        out["timing"] = tuple(x.value for x in ms)
+        return out
+
+    def subjects_handle(self, queries, global_max_depth=5):
+        """keto_subjects_batch -> the keto_subjects handle itself (a c_void_p): read it with
+        _subjects_arrays, give it back with lib.keto_subjects_free.  It outlives writes and the snapshot."""
+        keep = _Keep()
+        n = len(queries)
+        arr = (KSubjectsReq * max(1, n))()
+        for k, (ns, obj, rel, depth, size, page) in enumerate(queries):
+            arr[k].namespace_ = keep.s(ns)
+            arr[k].object = keep.s(obj)
+            arr[k].relation = keep.s(rel)
+            arr[k].max_depth = depth
+            arr[k].page_size = size
+            arr[k].page = page
+        h = C.c_void_p()
+        _check(self.lib.keto_subjects_batch(self.h, arr, C.c_uint32(n), C.c_int32(global_max_depth), C.byref(h)))
+        return h
+
+    def subjects_raw(self, queries, global_max_depth=5):
+        """keto_subjects_batch.  queries: (namespace, object, relation, max_depth, page_size, page), page_size
+        0 = the snapshot's and page 0 = the first -> a dict of arrays copied out of the keto_subjects
+        handle, which is freed here: status[n], offsets[n+1], ids (uint32 string ids, ascending per query),
+        next_page[n], totals[n], leaves[n], set_leaves[n], timing = (expand_ms, flatten_ms) and stages =
+        the flatten's five HIP-event times."""
+        h = self.subjects_handle(queries, global_max_depth)
+        try:
+            assert self.lib.keto_subjects_count(h) == len(queries)
+            return self._subjects_arrays(h)
+        finally:
+            self.lib.keto_subjects_free(h)
+
+    def subjects_ids_raw(self, roots, depths, sizes, pages, global_max_depth=5):
+        """keto_subjects_batch_ids: pre-resolved roots as in expand_batch_ids (every one a subject set's
+        row, bit 31 set), page sizes and pages as arrays -> the dict of subjects_raw."""
+        roots = np.ascontiguousarray(roots, dtype=np.uint32)
+        depths = np.ascontiguousarray(depths, dtype=np.int32)
+        sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
+        pages = np.ascontiguousarray(pages, dtype=np.uint32)
+        assert len(depths) == len(sizes) == len(pages) == len(roots)
+        h = C.c_void_p()
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        _check(self.lib.keto_subjects_batch_ids(self.h, ptr(roots), ptr(depths), ptr(sizes), ptr(pages),
+                                                C.c_uint32(len(roots)), C.c_int32(global_max_depth), C.byref(h)))
+        try:
+            return self._subjects_arrays(h)
+        finally:
+            self.lib.keto_subjects_free(h)
+
+    def subjects(self, queries, global_max_depth=5):
+        """Which subjects have a relation on an object (Expand flattened, not a check): queries as in
+        subjects_raw -> per query (status, [subject id strings in ascending string-id order], next page
+        token ("" = last page), total distinct subject ids, id leaves before deduplication, subject-set
+        leaves)."""
+        r = self.subjects_raw(queries, global_max_depth)
+        ids = [f[1] for f in self.subject_fields(r["ids"])] if len(r["ids"]) else []
+        offs = r["offsets"]
+        return [(int(r["status"][i]), ids[int(offs[i]):int(offs[i + 1])],
+                 str(int(r["next_page"][i])) if r["next_page"][i] else "", int(r["totals"][i]),
+                 int(r["leaves"][i]), int(r["set_leaves"][i])) for i in range(len(queries))]
 
     def subject_fields(self, refs, arena=None):
         """keto_subject_fields: per subject reference ("id", id) or ("set", namespace, object, relation)."""

@@ -1449,6 +1449,104 @@ int keto_looked_timing(const keto_looked* l, float* index_ms, float* candidates_
     });
 }
 
+// ---- keto_subjects_batch: the subjects that have a relation on an object (subjects.hip)
+struct keto_subjects {
+    SubjectsResult r;                       // r.ids: a block of the pinned pool, or NULL
+    ~keto_subjects() { pinned_give(r.ids); }
+};
+
+extern "C++" {
+// Lock order, as in expand_encode: rw shared -> D.mu (device_expand hands it over in `keep`) -> the
+// flatten's own mutex (h->subjects.mu).  subjects_flatten drops D.mu once its passes over the arena
+// have completed; whatever it leaves held goes with `keep`, before rw.
+template <class Expand>
+int subjects_call(keto_snapshot* h, const uint32_t* page_size, const uint32_t* page, keto_subjects** out, Expand expand) {
+    *out = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::shared_lock<RwGate> rlk(h->s->rw);        // one version from the expand to the page
+    Snapshot& S = *h->s;
+    if (!S.dev) throw Error{KETO_E_HIP, "snapshot has no device copy"};
+    if (S.part_mode == PART_MIGRATE && S.n_parts > 1)   // (before a root of another part is looked at)
+        throw Error{KETO_E_INVALID, "keto_subjects_batch is not available on a migrating part"};
+    keto_tree_arena a;                              // the call's overlay keys, statuses, offsets
+    ExpandOnDevice keep;
+    expand(S, a, &keep);
+    const auto t1 = std::chrono::steady_clock::now();
+    auto r = std::make_unique<keto_subjects>();
+    r->r.expand_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+    subjects_flatten(S, h->subjects, keep, a.r, page_size, page, (uint32_t)a.r.status.size(), r->r);
+    *out = r.release();
+    return KETO_OK;
+}
+}  // extern "C++"
+
+int keto_subjects_batch(keto_snapshot* h, const keto_subjects_req* reqs, uint32_t n, int32_t global_max_depth,
+                        keto_subjects** out) {
+    return guarded([&] {
+        if (!h || !out || (n && !reqs)) throw Error{KETO_E_INVALID, "NULL argument"};
+        std::vector<keto_expand_req> ex(n);
+        std::vector<uint32_t> size(n), page(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            ex[i] = keto_expand_req{};
+            ex[i].subject.kind = 1;
+            ex[i].subject.set_namespace = reqs[i].namespace_;
+            ex[i].subject.set_object = reqs[i].object;
+            ex[i].subject.set_relation = reqs[i].relation;
+            ex[i].max_depth = reqs[i].max_depth;
+            size[i] = reqs[i].page_size;
+            page[i] = reqs[i].page;
+        }
+        return subjects_call(h, size.data(), page.data(), out, [&](Snapshot& S, keto_tree_arena& a, ExpandOnDevice* keep) {
+            expand_named(S, ex.data(), n, global_max_depth, a, nullptr, keep);
+        });
+    });
+}
+
+int keto_subjects_batch_ids(keto_snapshot* h, const uint32_t* roots, const int32_t* max_depth, const uint32_t* page_size,
+                            const uint32_t* page, uint32_t n, int32_t global_max_depth, keto_subjects** out) {
+    return guarded([&] {
+        if (!h || !out || (n && (!roots || !max_depth || !page_size || !page))) throw Error{KETO_E_INVALID, "NULL argument"};
+        for (uint32_t i = 0; i < n; ++i)
+            if (!(roots[i] & EDGE_SET))
+                throw Error{KETO_E_INVALID, "keto_subjects_batch_ids: root " + std::to_string(i) + " is no subject set"};
+        return subjects_call(h, page_size, page, out, [&](Snapshot& S, keto_tree_arena& a, ExpandOnDevice* keep) {
+            expand_ids(S, roots, max_depth, n, global_max_depth, a, keep);
+        });
+    });
+}
+
+void keto_subjects_free(keto_subjects* r) { delete r; }
+
+uint32_t keto_subjects_count(const keto_subjects* r) { return r ? (uint32_t)r->r.status.size() : 0; }
+
+const uint32_t* keto_subjects_ids(const keto_subjects* r, uint64_t* total_out) {
+    if (total_out) *total_out = r ? r->r.offsets.back() : 0;
+    return r ? r->r.ids : nullptr;
+}
+
+const uint64_t* keto_subjects_offsets(const keto_subjects* r) { return r ? r->r.offsets.data() : nullptr; }
+
+const uint8_t* keto_subjects_status(const keto_subjects* r) { return r ? r->r.status.data() : nullptr; }
+
+const uint64_t* keto_subjects_next_page(const keto_subjects* r) { return r ? r->r.next_page.data() : nullptr; }
+
+const uint64_t* keto_subjects_totals(const keto_subjects* r) { return r ? r->r.totals.data() : nullptr; }
+
+const uint64_t* keto_subjects_leaves(const keto_subjects* r) { return r ? r->r.leaves.data() : nullptr; }
+
+const uint64_t* keto_subjects_set_leaves(const keto_subjects* r) { return r ? r->r.set_leaves.data() : nullptr; }
+
+int keto_subjects_timing(const keto_subjects* r, float* expand_ms, float* flatten_ms) {
+    return guarded([&] {
+        if (!r) throw Error{KETO_E_INVALID, "NULL argument"};
+        if (expand_ms) *expand_ms = r->r.expand_ms;
+        if (flatten_ms) *flatten_ms = r->r.flatten_ms;
+        return KETO_OK;
+    });
+}
+
+const float* keto_subjects_stages(const keto_subjects* r) { return r ? r->r.stage_ms : nullptr; }
+
 int keto_list_index_info(const keto_snapshot* h, keto_list_index_info_t* out) {
     return guarded([&] {
         if (!h || !out) throw Error{KETO_E_INVALID, "NULL argument"};

@@ -11,12 +11,16 @@
 
 #include "list.hpp"
 #include "snapshot.hpp"
+#include "subjects.hpp"
 
 struct keto_snapshot {
     std::unique_ptr<keto::Snapshot> s;
     // keto_list_batch / keto_list_plan: the list index of s's current version (list.hip), freed with
     // the handle, before s and its device state
     mutable keto::ListCache list;
+    // keto_subjects_batch: the flatten's device workspace and stream (subjects.hip), freed with the
+    // handle, before s and its device state
+    mutable keto::SubjectsCache subjects;
 };
 
 struct keto_tree_arena {
