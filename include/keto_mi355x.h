@@ -693,6 +693,52 @@ int keto_listed_timing(const keto_listed*, float* index_ms, float* scan_ms);
 typedef struct { uint64_t lo, hi; int64_t ns; uint32_t obj, rel, subject; uint8_t status; } keto_list_plan_t;
 int keto_list_plan(const keto_snapshot* s, const keto_list_req* reqs, uint32_t n, keto_list_plan_t* out);
 
+/* ---- List response bodies encoded on the device (repo:keto_amd/csrc/list.hip, proto.hip) ----
+ * keto_list_encode_batch answers the same queries as keto_list_batch with the bytes a handler sends,
+ * so the caller makes no keto_subject_fields call and marshals nothing:
+ *   KETO_ENC_JSON   json.Marshal(GetResponse) (internal/relationtuple/handler.go:23-29), no trailing
+ *                   newline: {"relation_tuples":[T,...],"next_page_token":"<decimal or empty>"} with
+ *                   T = {"namespace":..,"object":..,"relation":..,"subject_id":..} or
+ *                   ..,"subject_set":{"namespace":..,"object":..,"relation":..}} --
+ *                   InternalRelationTuple.MarshalJSON is ToQuery() (definitions.go:340-342,367-375), whose
+ *                   RelationQuery has this field order and omitempty on the two subject fields only
+ *                   (definitions.go:45-65), so empty strings print as "".  Strings are escaped as Go's
+ *                   encoding/json does with HTML escaping, exactly as in keto_tree_json_all.  An empty
+ *                   page is [] and never null (persistence/sql/relationtuples.go:267: make(..., len(res))).
+ *   KETO_ENC_PROTO  proto.Marshal(ListRelationTuplesResponse) (read_server.go:39-45,148-151;
+ *                   proto/ory/keto/acl/v1alpha1/read_service.proto:85-91, acl.proto:14-52; ToProto,
+ *                   definitions.go:231-250,358-365): per tuple 0x0A len M, M = the namespace (0x0A),
+ *                   object (0x12) and relation (0x1A) strings, each omitted when empty, and 0x22 len
+ *                   Subject, always present, its bytes as in keto_tree_proto_all (an id is present even
+ *                   when ""; a set's empty strings are omitted); then 0x12 len digits when the token is
+ *                   not empty.  An OK query without tuples and without a token has no bytes: the status
+ *                   tells it from a failed one.
+ * Statuses, next_page, totals and the page windows are exactly keto_list_batch's on the same requests,
+ * the poison rule and page_size 0 included.  A query that is not KETO_LIST_OK has an empty body (its two
+ * offsets are equal).  The herodot writer's framing around the JSON is the caller's.
+ * The result owns a block of the library's pinned pool and holds no reference to the snapshot: it
+ * stays readable after keto_snapshot_apply and keto_snapshot_release, until it is freed.  n = 0 gives
+ * count 0, offsets {0} and total 0.  Errors: an unknown encoding, out == NULL, or reqs == NULL with
+ * n > 0 is KETO_E_INVALID; then as keto_list_batch: a host-only snapshot is KETO_E_HIP whatever n is, a
+ * part of a partitioned upload KETO_E_INVALID.  More than 2^31 tuples in one call is KETO_E_RANGE.
+ * Device memory beyond the list call's: 16 B per tuple of the pages plus the bodies.
+ * KETO_LIST_ENC_LDS=0 (environment, read per call) makes every wave of the write kernel write straight
+ * to global memory instead of staging its items in LDS; the bytes are the same. */
+typedef struct keto_list_encoded keto_list_encoded;
+int keto_list_encode_batch(keto_snapshot* s, const keto_list_req* reqs, uint32_t n,
+                           uint32_t encoding /* KETO_ENC_PROTO | KETO_ENC_JSON */, keto_list_encoded** out);
+void            keto_list_encoded_free(keto_list_encoded*);                 /* NULL is fine */
+uint32_t        keto_list_encoded_count(const keto_list_encoded*);
+const uint8_t*  keto_list_encoded_bytes(const keto_list_encoded*, uint64_t* total_out); /* NULL when total is 0 */
+const uint64_t* keto_list_encoded_offsets(const keto_list_encoded*);       /* n+1; body i = bytes[off[i], off[i+1]) */
+const uint8_t*  keto_list_encoded_status(const keto_list_encoded*);        /* n x KETO_LIST_* */
+const uint64_t* keto_list_encoded_next_page(const keto_list_encoded*);
+const uint64_t* keto_list_encoded_totals(const keto_list_encoded*);
+const uint64_t* keto_list_encoded_tuples(const keto_list_encoded*);        /* n: tuples encoded into body i */
+/* index_ms and scan_ms as keto_listed_timing (scan_ms ends with the emit pass: no tuple leaves the
+ * device); encode_ms = sizes, scan, write and the bytes' D2H (HIP events on the list stream) */
+int keto_list_encoded_timing(const keto_list_encoded*, float* index_ms, float* scan_ms, float* encode_ms);
+
 /* The list index across writes (repo:keto_amd/csrc/list.hip).  keto_snapshot_apply leaves the index as
  * it is and only notes the ids of the rows it changed in a journal (a deduplicated set, relative to the
  * version the index describes).  The first list call after one or more writes patches the index from

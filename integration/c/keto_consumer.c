@@ -511,6 +511,94 @@ static void subject_of(line_t* l, int* k, keto_subject* s) {
     }
 }
 
+static void put_quoted(buf_t* b, const char* s, size_t n) { /* this program's data needs no escaping */
+    put(b, "\"", 1);
+    put(b, s, n);
+    put(b, "\"", 1);
+}
+#define PUT_S(b, lit) put((b), (lit), sizeof(lit) - 1)
+
+/* The same query through keto_list_encode_batch in JSON: status, token, total and tuple count are those
+ * of the keto_list_batch result l, and the body is the json.Marshal(GetResponse) text composed here from
+ * l's tuples and keto_subject_fields (size, then fill).  Returns 0 when everything agrees. */
+static int list_body_check(keto_snapshot* s, const keto_list_req* q, const keto_listed* l) {
+    keto_list_encoded* e = NULL;
+    const int rc = keto_list_encode_batch(s, q, 1, KETO_ENC_JSON, &e);
+    if (rc != KETO_OK) fail("keto_list_encode_batch", rc);
+    uint64_t n = 0, total = 0;
+    const keto_list_tuple* t = keto_listed_tuples(l, &n);
+    const uint8_t* body = keto_list_encoded_bytes(e, &total);
+    const uint64_t* off = keto_list_encoded_offsets(e);
+    const uint8_t status = keto_list_encoded_status(e)[0];
+    const uint64_t next = keto_list_encoded_next_page(e)[0];
+    int bad = keto_list_encoded_count(e) != 1 || off[0] != 0 || off[1] != total ||
+              status != keto_listed_status(l)[0] || next != keto_listed_next_page(l)[0] ||
+              keto_list_encoded_totals(e)[0] != keto_listed_totals(l)[0] || keto_list_encoded_tuples(e)[0] != n;
+    buf_t want;
+    memset(&want, 0, sizeof want);
+    if (!bad && status == KETO_LIST_OK) {
+        uint32_t* refs = (uint32_t*)malloc((2 * n + 1) * sizeof(uint32_t));
+        uint32_t* lens = (uint32_t*)malloc((6 * n + 1) * sizeof(uint32_t));
+        if (!refs || !lens) return 3;
+        for (uint64_t k = 0; k < n; ++k) {
+            refs[2 * k] = t[k].row | 0x80000000u;
+            refs[2 * k + 1] = t[k].subject;
+        }
+        const int64_t bytes = n ? keto_subject_fields(s, NULL, refs, 2 * n, NULL, 0, lens) : 0;
+        if (bytes < 0) fail("keto_subject_fields", (int)bytes);
+        char* text = (char*)malloc((size_t)bytes + 1);
+        if (!text) return 3;
+        if (n && keto_subject_fields(s, NULL, refs, 2 * n, text, (uint64_t)bytes, lens) != bytes) bad = 1;
+        const char* p = text;
+        PUT_S(&want, "{\"relation_tuples\":[");
+        for (uint64_t k = 0; k < n && !bad; ++k) {
+            const uint32_t* kl = lens + 6 * k;                 /* the row's three, then the subject's */
+            if (k) PUT_S(&want, ",");
+            PUT_S(&want, "{\"namespace\":");
+            put_quoted(&want, p, kl[0]);
+            p += kl[0];
+            PUT_S(&want, ",\"object\":");
+            put_quoted(&want, p, kl[1]);
+            p += kl[1];
+            PUT_S(&want, ",\"relation\":");
+            put_quoted(&want, p, kl[2]);
+            p += kl[2];
+            if (t[k].subject & 0x80000000u) {
+                PUT_S(&want, ",\"subject_set\":{\"namespace\":");
+                put_quoted(&want, p, kl[3]);
+                p += kl[3];
+                PUT_S(&want, ",\"object\":");
+                put_quoted(&want, p, kl[4]);
+                p += kl[4];
+                PUT_S(&want, ",\"relation\":");
+                put_quoted(&want, p, kl[5]);
+                p += kl[5];
+                PUT_S(&want, "}}");
+            } else {
+                PUT_S(&want, ",\"subject_id\":");
+                put_quoted(&want, p, kl[3]);
+                p += kl[3];
+                PUT_S(&want, "}");
+            }
+        }
+        PUT_S(&want, "],\"next_page_token\":\"");
+        if (next) {
+            char digits[24];
+            const int d = snprintf(digits, sizeof digits, "%llu", (unsigned long long)next);
+            put(&want, digits, (size_t)d);
+        }
+        PUT_S(&want, "\"}");
+        free(text);
+        free(refs);
+        free(lens);
+    }
+    bad |= want.n != total || (total && memcmp(want.p, body, total) != 0);
+    printf("list-json\t%d\t%u\t%llu\n", rc, status, (unsigned long long)total);
+    free(want.p);
+    keto_list_encoded_free(e);
+    return bad ? 16 : 0;
+}
+
 /* One list round trip (keto_list_batch, ListRelationTuples from the snapshot): the first page of the
  * unfiltered query, i.e. of every tuple of the table.  A host-only snapshot must fail with KETO_E_HIP
  * and a part of a partitioned upload with KETO_E_INVALID.  On a device the page holds min(page size,
@@ -554,6 +642,7 @@ static int list_round_trip(keto_snapshot* s, int device, int n_parts, uint32_t p
     } else {
         bad |= status != KETO_LIST_NOT_FOUND || n != 0;   /* no subject filter: never undecided */
     }
+    bad |= list_body_check(s, &q, l);
     printf("list\t%d\t%u\t%llu\t%llu\t%llu\n", rc, status, (unsigned long long)n, (unsigned long long)total,
            (unsigned long long)next);
     keto_listed_free(l);

@@ -840,6 +840,80 @@ func (s *Snapshot) ListBatch(qs []ListQuery) ([]ListResult, error) {
 	return out, nil
 }
 
+// Encodings of ListEncodeBatch (KETO_ENC_*).
+const (
+	EncProto = int(C.KETO_ENC_PROTO) // proto.Marshal(ListRelationTuplesResponse)
+	EncJSON  = int(C.KETO_ENC_JSON)  // json.Marshal(GetResponse), no trailing newline
+)
+
+// ListBody is one query's response body, encoded on the device: what a handler sends.  Body is set
+// only when Status is ListOK (and may still be empty: a protobuf response without tuples and without a
+// token has no bytes); Tuples is the number of tuples in it.
+type ListBody struct {
+	Status   uint8
+	Body     []byte
+	NextPage uint64
+	Total    uint64
+	Tuples   uint64
+}
+
+// ListEncodeBatch answers the queries of ListBatch with their response bodies
+// (keto_list_encode_batch): the page's tuples never leave the device, no string is looked up and
+// nothing is marshalled here.  enc is EncJSON (GET /relation-tuples: write Body where the handler would
+// h.d.Writer().Write the GetResponse) or EncProto (ReadService.ListRelationTuples).  Statuses, tokens
+// and totals are ListBatch's.  Not for a Partition.
+func (s *Snapshot) ListEncodeBatch(qs []ListQuery, enc int) ([]ListBody, error) {
+	n := len(qs)
+	if n == 0 {
+		return nil, nil
+	}
+	var m cmem
+	defer m.free()
+	total := 0
+	for i := range qs {
+		total += len(qs[i].Namespace) + len(qs[i].Object) + len(qs[i].Relation) + subjectLen(qs[i].Subject)
+	}
+	m.strings(total)
+	cr := (*C.keto_list_req)(m.alloc(n * int(C.sizeof_keto_list_req)))
+	cs := unsafe.Slice(cr, n)
+	for i := range qs {
+		q := &qs[i]
+		cs[i] = C.keto_list_req{namespace_: m.s(q.Namespace), object: m.s(q.Object), relation: m.s(q.Relation),
+			page_size: C.uint32_t(q.PageSize), page: C.uint32_t(q.Page)}
+		if q.Subject != nil {
+			cs[i].has_subject = 1
+			cs[i].subject = m.subject(q.Subject)
+		}
+	}
+	var l *C.keto_list_encoded
+	if rc := C.keto_list_encode_batch(s.h, cr, C.uint32_t(n), C.uint32_t(enc), &l); rc != C.KETO_OK {
+		return nil, lastErr(rc)
+	}
+	defer C.keto_list_encoded_free(l)
+	var count C.uint64_t
+	bp := C.keto_list_encoded_bytes(l, &count)
+	off := unsafe.Slice(C.keto_list_encoded_offsets(l), n+1)
+	status := unsafe.Slice(C.keto_list_encoded_status(l), n)
+	next := unsafe.Slice(C.keto_list_encoded_next_page(l), n)
+	totals := unsafe.Slice(C.keto_list_encoded_totals(l), n)
+	tuples := unsafe.Slice(C.keto_list_encoded_tuples(l), n)
+	// one copy out of the result's pinned block; the bodies are slices of it
+	var all []byte
+	if bp != nil && count > 0 {
+		all = make([]byte, int(count))
+		copy(all, unsafe.Slice((*byte)(unsafe.Pointer(bp)), int(count)))
+	}
+	out := make([]ListBody, n)
+	for i := 0; i < n; i++ {
+		out[i] = ListBody{Status: uint8(status[i]), NextPage: uint64(next[i]), Total: uint64(totals[i]),
+			Tuples: uint64(tuples[i])}
+		if out[i].Status == ListOK {
+			out[i].Body = all[int(off[i]):int(off[i+1]):int(off[i+1])]
+		}
+	}
+	return out, nil
+}
+
 // Lookup statuses of LookupObjects (KETO_LOOKUP_*).
 const (
 	LookupOK               = uint8(C.KETO_LOOKUP_OK)

@@ -47,6 +47,9 @@ EXPORTS = [
     "keto_list_batch", "keto_listed_free", "keto_listed_count", "keto_listed_tuples", "keto_listed_offsets",
     "keto_listed_status", "keto_listed_next_page", "keto_listed_totals", "keto_listed_timing", "keto_list_plan",
     "keto_snapshot_delete_query", "keto_list_index_info",
+    "keto_list_encode_batch", "keto_list_encoded_free", "keto_list_encoded_count", "keto_list_encoded_bytes",
+    "keto_list_encoded_offsets", "keto_list_encoded_status", "keto_list_encoded_next_page", "keto_list_encoded_totals",
+    "keto_list_encoded_tuples", "keto_list_encoded_timing",
     "keto_lookup_objects_batch", "keto_looked_free", "keto_looked_count", "keto_looked_rows", "keto_looked_offsets",
     "keto_looked_status", "keto_looked_next_page", "keto_looked_totals", "keto_looked_candidates",
     "keto_looked_undecided", "keto_looked_timing",
@@ -274,6 +277,20 @@ def load():
             f.restype = C.c_void_p
             f.argtypes = [C.c_void_p]
         lib.keto_listed_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    if hasattr(lib, "keto_list_encode_batch"):
+        lib.keto_list_encode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+        lib.keto_list_encoded_free.restype = None
+        lib.keto_list_encoded_free.argtypes = [C.c_void_p]
+        lib.keto_list_encoded_count.restype = C.c_uint32
+        lib.keto_list_encoded_count.argtypes = [C.c_void_p]
+        lib.keto_list_encoded_bytes.restype = C.c_void_p
+        lib.keto_list_encoded_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        for f in (lib.keto_list_encoded_offsets, lib.keto_list_encoded_status, lib.keto_list_encoded_next_page,
+                  lib.keto_list_encoded_totals, lib.keto_list_encoded_tuples):
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p]
+        lib.keto_list_encoded_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_float)]
     if hasattr(lib, "keto_lookup_objects_batch"):
         lib.keto_looked_free.restype = None
         lib.keto_looked_free.argtypes = [C.c_void_p]
@@ -955,6 +972,45 @@ class Snapshot:
         status, offs, tup, nxt, tot, _ = self.list_batch_raw(queries)
         dec = self.decode_list_tuples(tup)
         return [(int(status[i]), dec[int(offs[i]):int(offs[i + 1])], str(int(nxt[i])) if nxt[i] else "", int(tot[i]))
+                for i in range(len(queries))]
+
+    def list_encode_raw(self, queries, encoding="json"):
+        """keto_list_encode_batch.  queries as in list_batch; encoding "json" / "proto" (or KETO_ENC_*)
+        -> a dict of arrays copied out of the keto_list_encoded handle, which is freed here: status[n],
+        offsets[n+1], bytes (uint8), next_page[n], totals[n], tuples[n] and timing = (index_ms, scan_ms,
+        encode_ms)."""
+        keep = _Keep()
+        n = len(queries)
+        enc = ENCODINGS.get(encoding, encoding)
+        h = C.c_void_p()
+        _check(self.lib.keto_list_encode_batch(self.h, self._list_reqs(keep, queries), C.c_uint32(n), C.c_uint32(enc),
+                                               C.byref(h)))
+        try:
+            assert self.lib.keto_list_encoded_count(h) == n
+            total = C.c_uint64()
+            p = self.lib.keto_list_encoded_bytes(h, C.byref(total))
+            get = lambda f, nbytes, dt: np.frombuffer(C.string_at(f(h), nbytes), dtype=dt).copy()
+            out = {"status": get(self.lib.keto_list_encoded_status, n, np.uint8),
+                   "offsets": get(self.lib.keto_list_encoded_offsets, 8 * (n + 1), np.uint64),
+                   "next_page": get(self.lib.keto_list_encoded_next_page, 8 * n, np.uint64),
+                   "totals": get(self.lib.keto_list_encoded_totals, 8 * n, np.uint64),
+                   "tuples": get(self.lib.keto_list_encoded_tuples, 8 * n, np.uint64),
+                   "bytes": (np.frombuffer(C.string_at(p, total.value), dtype=np.uint8).copy() if total.value
+                             else np.zeros(0, dtype=np.uint8))}
+            ims, sms, ems = C.c_float(), C.c_float(), C.c_float()
+            _check(self.lib.keto_list_encoded_timing(h, C.byref(ims), C.byref(sms), C.byref(ems)))
+            out["timing"] = (ims.value, sms.value, ems.value)
+        finally:
+            self.lib.keto_list_encoded_free(h)
+        return out
+
+    def list_encode(self, queries, encoding="json"):
+        """ListRelationTuples response bodies for a batch, encoded on the device: per query (status, body
+        bytes (b"" unless the status is KETO_LIST_OK), next page token, total matches, tuples in the body)."""
+        r = self.list_encode_raw(queries, encoding)
+        raw, offs = r["bytes"].tobytes(), r["offsets"]
+        return [(int(r["status"][i]), raw[int(offs[i]):int(offs[i + 1])],
+                 str(int(r["next_page"][i])) if r["next_page"][i] else "", int(r["totals"][i]), int(r["tuples"][i]))
                 for i in range(len(queries))]
 
     # ------------------------------------------------------------------ reverse lookup

@@ -1398,6 +1398,57 @@ int keto_listed_timing(const keto_listed* l, float* index_ms, float* scan_ms) {
     });
 }
 
+// ---- keto_list_encode_batch: the same queries answered as response bodies (list.hip, proto.hip)
+struct keto_list_encoded {
+    ListEncoded r;                          // r.bytes: a block of the pinned pool, or NULL
+    ~keto_list_encoded() { pinned_give(r.bytes); }
+};
+
+int keto_list_encode_batch(keto_snapshot* h, const keto_list_req* reqs, uint32_t n, uint32_t encoding,
+                           keto_list_encoded** out) {
+    return guarded([&] {
+        if (!h || !out || (n && !reqs)) throw Error{KETO_E_INVALID, "NULL argument"};
+        *out = nullptr;
+        // Lock order: rw shared -> the list mutex (list_encode_batch) -> S.mu (the encoder, which holds
+        // proto_state and its work buffers).  No holder of S.mu takes the list mutex, and writers take
+        // the list mutex only under rw exclusive, which this call excludes.
+        std::shared_lock<RwGate> lk(h->s->rw);
+        auto l = std::make_unique<keto_list_encoded>();
+        list_encode_batch(*h->s, h->list, reqs, n, encoding, l->r);
+        *out = l.release();
+        return KETO_OK;
+    });
+}
+
+void keto_list_encoded_free(keto_list_encoded* l) { delete l; }
+
+uint32_t keto_list_encoded_count(const keto_list_encoded* l) { return l ? (uint32_t)l->r.r.status.size() : 0; }
+
+const uint8_t* keto_list_encoded_bytes(const keto_list_encoded* l, uint64_t* total_out) {
+    if (total_out) *total_out = l ? l->r.total : 0;
+    return l ? l->r.bytes : nullptr;
+}
+
+const uint64_t* keto_list_encoded_offsets(const keto_list_encoded* l) { return l ? l->r.offsets.data() : nullptr; }
+
+const uint8_t* keto_list_encoded_status(const keto_list_encoded* l) { return l ? l->r.r.status.data() : nullptr; }
+
+const uint64_t* keto_list_encoded_next_page(const keto_list_encoded* l) { return l ? l->r.r.next_page.data() : nullptr; }
+
+const uint64_t* keto_list_encoded_totals(const keto_list_encoded* l) { return l ? l->r.r.totals.data() : nullptr; }
+
+const uint64_t* keto_list_encoded_tuples(const keto_list_encoded* l) { return l ? l->r.tuples.data() : nullptr; }
+
+int keto_list_encoded_timing(const keto_list_encoded* l, float* index_ms, float* scan_ms, float* encode_ms) {
+    return guarded([&] {
+        if (!l) throw Error{KETO_E_INVALID, "NULL argument"};
+        if (index_ms) *index_ms = l->r.r.index_ms;
+        if (scan_ms) *scan_ms = l->r.r.scan_ms;
+        if (encode_ms) *encode_ms = l->r.encode_ms;
+        return KETO_OK;
+    });
+}
+
 // ---- keto_lookup_objects_batch: the objects a subject has a relation on (list.hip)
 struct keto_looked {
     LookupResult r;                         // r.rows: a block of the pinned pool, or NULL

@@ -1287,48 +1287,42 @@ struct GroupedCount {
     }
 };
 
-}  // namespace
+// What the count, scan and emit passes of a batch leave behind, before any tuple goes to the host: the
+// page's entries in L.out at the windows' offsets (a page holding a poisoned entry included: its
+// flag is d_qpage[q], still on the device), the windows on both sides, and the statuses, tokens and
+// totals as far as the host knows them (out.status / next_page / totals: all but the page-poison rule).
+struct ListPasses {
+    std::vector<LQuery> qs;
+    std::vector<LWindow> wins;
+    uint64_t total_out = 0;
+    uint2* d_out = nullptr;                  // total_out entries (NULL when there are none)
+    LWindow* d_wins = nullptr;               // n (uploaded when there are entries, or on request)
+    uint32_t* d_qpage = nullptr;             // n
+    EventPair ev;                            // ev.a: recorded in front of the passes, on L.stream
+};
 
-void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, ListResult& out) {
-    if (S.n_parts > 1) throw Error{KETO_E_INVALID, "keto_list_batch: a part of a partitioned snapshot holds only some rows"};
-    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
-    out.status.assign(n, KETO_LIST_OK);
-    out.offsets.assign((uint64_t)n + 1, 0);
-    out.next_page.assign(n, 0);
-    out.totals.assign(n, 0);
-    out.tuples = nullptr;
-    out.index_ms = out.scan_ms = 0;
-    if (n == 0) return;
-    const uint32_t tile = list_tile();
-    std::lock_guard<std::mutex> lk(C.mu);                    // one list call at a time per snapshot
-    ListState& L = current_index(S, C, V.device, out.index_ms);
+// The caller holds C.mu and has the index current.  Everything is enqueued on L.stream; the one host
+// sync between the passes is inside.  want_wins: upload the windows also when no entry is emitted.
+void list_passes(Snapshot& S, ListState& L, const keto_list_req* reqs, uint32_t n, uint32_t tile, bool want_wins,
+                 ListResult& out, ListPasses& P) {
     hipStream_t st = L.stream;
 
     // ---- resolve (host threads)
-    std::vector<LQuery> qs(n);
+    std::vector<LQuery>& qs = P.qs;
+    qs.resize(n);
     const unsigned th = n >= 4096 ? build_threads() : 1u;
     par_chunks(n, th, 1024, [&](uint64_t b, uint64_t e, unsigned) {
         for (uint64_t i = b; i < e; ++i) {
-            const Plan P = resolve_list(S, L, reqs[i]);
-            qs[i] = P.q;
-            out.status[i] = P.status;
+            const Plan Pl = resolve_list(S, L, reqs[i]);
+            qs[i] = Pl.q;
+            out.status[i] = Pl.status;
         }
     });
     LQuery* d_qs = L.qs.get<LQuery>(n);
     uint64_t* d_tot = L.tot.get<uint64_t>(n);
     uint32_t* d_qpoison = L.qpoison.get<uint32_t>(n);
     uint32_t* d_qpage = L.qpage.get<uint32_t>(n);
-    hipEvent_t e0, e1;
-    HIP_OK(hipEventCreate(&e0));
-    HIP_OK(hipEventCreate(&e1));
-    struct Events {
-        hipEvent_t a, b;
-        ~Events() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
-        }
-    } events{e0, e1};
-    HIP_OK(hipEventRecord(e0, st));
+    HIP_OK(hipEventRecord(P.ev.a, st));
     HIP_OK(hipMemcpyAsync(d_qs, qs.data(), (uint64_t)n * sizeof(LQuery), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(d_tot, 0, (uint64_t)n * sizeof(uint64_t), st));
     HIP_OK(hipMemsetAsync(d_qpoison, 0, (uint64_t)n * sizeof(uint32_t), st));
@@ -1345,7 +1339,8 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
     HIP_OK(hipMemcpyAsync(tot.data(), d_tot, (uint64_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(qpoison.data(), d_qpoison, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    std::vector<LWindow> wins(n);
+    std::vector<LWindow>& wins = P.wins;
+    wins.resize(n);
     uint64_t total_out = 0;
     for (uint32_t i = 0; i < n; ++i) {
         wins[i] = LWindow{0, 0, total_out};
@@ -1364,31 +1359,65 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
         wins[i].whi = first + k;
         total_out += k;
     }
+    P.total_out = total_out;
+    P.d_qpage = d_qpage;
+    if (total_out || want_wins) {
+        P.d_wins = L.wins.get<LWindow>(n);
+        HIP_OK(hipMemcpyAsync(P.d_wins, wins.data(), (uint64_t)n * sizeof(LWindow), hipMemcpyHostToDevice, st));
+    }
+    if (total_out) {
+        uint2* d_out = P.d_out = L.out.get<uint2>(total_out);
+        for (size_t g = 0; g < G.n_groups(); ++g) {
+            const uint32_t m = G.one_group() ? m_last : G.count(g);
+            if (m == 0) continue;
+            hipLaunchKernelGGL(list_emit, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, (const LItem*)L.items.p, tile,
+                               (const uint32_t*)L.cnt.p, (const uint32_t*)L.wcnt.p, (const uint64_t*)L.base.p,
+                               (const uint32_t*)L.ioff.p, G.groups[g], P.d_wins, d_out, total_out, d_qpage);
+            HIP_OK(hipGetLastError());
+        }
+    }
+}
+
+// what every list call checks and clears first
+void list_begin(const Snapshot& S, uint32_t n, ListResult& out) {
+    out.status.assign(n, KETO_LIST_OK);
+    out.offsets.assign((uint64_t)n + 1, 0);
+    out.next_page.assign(n, 0);
+    out.totals.assign(n, 0);
+    out.tuples = nullptr;
+    out.index_ms = out.scan_ms = 0;
+}
+
+}  // namespace
+
+void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, ListResult& out) {
+    if (S.n_parts > 1) throw Error{KETO_E_INVALID, "keto_list_batch: a part of a partitioned snapshot holds only some rows"};
+    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
+    list_begin(S, n, out);
+    if (n == 0) return;
+    const uint32_t tile = list_tile();
+    std::lock_guard<std::mutex> lk(C.mu);                    // one list call at a time per snapshot
+    ListState& L = current_index(S, C, V.device, out.index_ms);
+    hipStream_t st = L.stream;
+    ListPasses P;
+    list_passes(S, L, reqs, n, tile, /*want_wins=*/false, out, P);
+    const std::vector<LWindow>& wins = P.wins;
+    const uint64_t total_out = P.total_out;
+
     std::vector<uint32_t> qpage(n, 0);
     struct Block {                                          // the result's pinned block until it is handed over
         void* p = nullptr;
         ~Block() { pinned_give(p); }
     } block;
     if (total_out) {
-        LWindow* d_wins = L.wins.get<LWindow>(n);
-        uint2* d_out = L.out.get<uint2>(total_out);
-        HIP_OK(hipMemcpyAsync(d_wins, wins.data(), (uint64_t)n * sizeof(LWindow), hipMemcpyHostToDevice, st));
-        for (size_t g = 0; g < G.n_groups(); ++g) {
-            const uint32_t m = G.one_group() ? m_last : G.count(g);
-            if (m == 0) continue;
-            hipLaunchKernelGGL(list_emit, dim3(m), dim3(LIST_THREADS), 0, st, L.T, L.keys, d_qs, (const LItem*)L.items.p, tile,
-                               (const uint32_t*)L.cnt.p, (const uint32_t*)L.wcnt.p, (const uint64_t*)L.base.p,
-                               (const uint32_t*)L.ioff.p, G.groups[g], d_wins, d_out, total_out, d_qpage);
-            HIP_OK(hipGetLastError());
-        }
         block.p = pinned_take(total_out * sizeof(keto_list_tuple));
         static_assert(sizeof(keto_list_tuple) == sizeof(uint2), "a list tuple is an index entry");
-        HIP_OK(hipMemcpyAsync(block.p, d_out, total_out * sizeof(uint2), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(qpage.data(), d_qpage, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(block.p, P.d_out, total_out * sizeof(uint2), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(qpage.data(), P.d_qpage, (uint64_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
-    HIP_OK(hipEventRecord(e1, st));
+    HIP_OK(hipEventRecord(P.ev.b, st));
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipEventElapsedTime(&out.scan_ms, e0, e1));
+    HIP_OK(hipEventElapsedTime(&out.scan_ms, P.ev.a, P.ev.b));
 
     // ---- offsets; a page holding a poisoned tuple fails as a whole (toInternal over the page)
     keto_list_tuple* tup = static_cast<keto_list_tuple*>(block.p);
@@ -1408,6 +1437,51 @@ void list_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n
     out.offsets[n] = w;
     out.tuples = tup;
     block.p = nullptr;
+}
+
+// keto_list_encode_batch: the same passes, then the encoder (proto.hip) over the entries where list_emit
+// left them.  The encoder takes S.mu under C.mu (the order: rw shared -> C.mu -> S.mu) and runs on the
+// list stream; C.mu is not released while a kernel that reads L.out may be in flight.
+void list_encode_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uint32_t n, uint32_t encoding,
+                       ListEncoded& out) {
+    if (encoding != KETO_ENC_PROTO && encoding != KETO_ENC_JSON)
+        throw Error{KETO_E_INVALID, "unknown encoding " + std::to_string(encoding)};
+    if (S.n_parts > 1)
+        throw Error{KETO_E_INVALID, "keto_list_encode_batch: a part of a partitioned snapshot holds only some rows"};
+    const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
+    list_begin(S, n, out.r);
+    out.tuples.assign(n, 0);
+    out.bytes = nullptr;
+    out.total = 0;
+    out.encode_ms = 0;
+    if (n == 0) return;
+    const uint32_t tile = list_tile();
+    std::lock_guard<std::mutex> lk(C.mu);
+    ListState& L = current_index(S, C, V.device, out.r.index_ms);
+    hipStream_t st = L.stream;
+    struct Drain {                                           // also when anything below throws
+        hipStream_t st;
+        ~Drain() { (void)hipStreamSynchronize(st); }
+    } drain{st};
+    ListPasses P;
+    list_passes(S, L, reqs, n, tile, /*want_wins=*/true, out.r, P);
+    HIP_OK(hipEventRecord(P.ev.b, st));
+    static_assert(sizeof(LWindow) == 3 * sizeof(uint64_t), "the encoder reads a window as three words");
+    // per query: the token's number, or LIST_ENC_FAILED for a query that is not OK on the host's side
+    std::vector<uint64_t> meta(n);
+    for (uint32_t i = 0; i < n; ++i) meta[i] = out.r.status[i] == KETO_LIST_OK ? out.r.next_page[i] : LIST_ENC_FAILED;
+    ListEncodeIn in{P.d_out, P.total_out, reinterpret_cast<const uint64_t*>(P.d_wins), P.d_qpage, meta.data(), n, st};
+    std::vector<uint32_t> qpage;
+    device_list_encode(S, in, encoding, out, qpage);
+    HIP_OK(hipEventElapsedTime(&out.r.scan_ms, P.ev.a, P.ev.b));
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t k = P.wins[i].whi - P.wins[i].wlo;
+        if (k && qpage[i]) {                                 // the page-poison rule, as in list_batch
+            out.r.status[i] = KETO_LIST_NOT_FOUND;
+            out.r.totals[i] = 0;
+            out.r.next_page[i] = 0;
+        }
+    }
 }
 
 // ---- keto_snapshot_delete_query: the rows a query touches, and the index after the delete

@@ -35,6 +35,39 @@ void list_plan(const Snapshot& s, ListCache& c, const keto_list_req* reqs, uint3
 void list_batch(Snapshot& s, ListCache& c, const keto_list_req* reqs, uint32_t n, ListResult& out);
 uint64_t list_device_bytes(ListCache& c);   // device memory of the list index (0 before the first list_batch)
 
+// keto_list_encode_batch (list.hip, proto.hip): the response bodies of the same queries, encoded on the
+// device from the page's entries where list_emit left them
+struct ListEncoded {
+    ListResult r;                                       // status, next_page, totals, timings; r.offsets / r.tuples unused
+    std::vector<uint64_t> offsets, tuples;              // n + 1 byte offsets; n: tuples encoded into body i
+    uint8_t* bytes = nullptr;                           // a block of the pinned pool (pinned_take), or NULL (total 0)
+    uint64_t total = 0;
+    float encode_ms = 0;
+};
+// The caller holds the snapshot's lock shared.  Takes c.mu, and S.mu inside it (the encoder); out.bytes
+// goes to the caller, who gives it back with pinned_give -- also when the call throws.
+void list_encode_batch(Snapshot& s, ListCache& c, const keto_list_req* reqs, uint32_t n, uint32_t encoding,
+                       ListEncoded& out);
+// What list.hip hands the encoder in proto.hip: the page's entries {row id, subject word} of all queries
+// (d_slots, n_slots of them) and per query its window {wlo, whi, off} (three words: entries
+// d_slots[off, off + whi - wlo)), its poison-in-page flag -- all on the device, their writes enqueued on
+// `stream` -- and on the host meta[q] = the next page's number (0: none), or LIST_ENC_FAILED for a query
+// that is not KETO_LIST_OK whatever its page holds.
+constexpr uint64_t LIST_ENC_FAILED = ~0ull;
+struct ListEncodeIn {
+    const void* d_slots;
+    uint64_t n_slots;
+    const uint64_t* d_wins;
+    const uint32_t* d_qpage;
+    const uint64_t* meta;
+    uint32_t n;
+    void* stream;
+};
+// Runs on in.stream, under S.mu, after the refresh of the snapshot's strings on the device; returns with
+// the stream drained.  Fills out.offsets / tuples / bytes / total / encode_ms and qpage (the flags, on the host).
+void device_list_encode(Snapshot& s, const ListEncodeIn& in, uint32_t encoding, ListEncoded& out,
+                        std::vector<uint32_t>& qpage);
+
 // keto_lookup_objects_batch (list.hip): per query the tuple rows (namespace, o, relation), in key
 // order, whose check against the query's subject is allowed; the page of them
 struct LookupResult {

@@ -32,6 +32,7 @@
 
 #include "hip_check.hpp"
 #include "json_runs.hpp"
+#include "list.hpp"
 #include "parallel.hpp"
 #include "snapshot.hpp"
 
@@ -594,6 +595,10 @@ struct ProtoWork {
     PBuf ons, oobj, orel, nodes, toff, slen, size, st, root, hdr, pos, out, to, tmp, tmp3, lw, lp, uni, lu;
     PBuf jown, jclen, jcat, jpre, jcend, jcoff, jterm, jrun, jnil;      // device_tree_json's
 };
+// device_list_encode's, kept across calls likewise: 16 B per item (size, position), the bodies
+struct ListEncWork {
+    PBuf meta, sz, pos, res, tmp, out;
+};
 
 }  // namespace
 
@@ -611,6 +616,8 @@ struct ProtoState {
     uint64_t pin_bytes = 0;
     ProtoWork work;
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
+    ListEncWork list_work;
+    hipEvent_t list_ev = nullptr;     // orders the list stream behind a refresh (device_list_encode)
     void release_rows() {
         if (row_ns) (void)hipFree(row_ns);
         if (row_obj) (void)hipFree(row_obj);
@@ -627,6 +634,7 @@ struct ProtoState {
             if (pin[i]) (void)hipHostFree(pin[i]);
             if (pin_ev[i]) (void)hipEventDestroy(pin_ev[i]);
         }
+        if (list_ev) (void)hipEventDestroy(list_ev);
     }
 };
 
@@ -987,6 +995,430 @@ uint64_t device_tree_json_resident(Snapshot& S, const ResidentArena& res, const 
                                    uint64_t* offsets) {
     return encode_json(S, nullptr, &res, res.n_nodes, tree_off, nil, n_trees, ov_base, ov_keys, extra_base, extra,
                      Sink{nullptr, 0, bytes_out}, offsets);
+}
+
+// ---- keto_list_encode_batch: the ListRelationTuples response bodies of a batch of list queries, from
+// the page's entries where list_emit left them (list.hip) and the tables above.  Paths relative to the
+// reference tree: json.Marshal of GetResponse (internal/relationtuple/handler.go:23-29), whose tuples
+// marshal as their RelationQuery (definitions.go:340-342,367-375: MarshalJSON is ToQuery(); :45-65: the
+// field order, omitempty on the two subject fields), or proto.Marshal of ListRelationTuplesResponse
+// (read_server.go:39-45,148-151; ToProto, definitions.go:231-250,358-365; acl.proto:14-52,
+// read_service.proto:85-91).  An empty page is [] (persistence/sql/relationtuples.go:267), never null.
+//
+// The output is flat: query q owns the items [off_q + 2 q, off_q + 2 q + k_q + 2) -- a head frame, its
+// k_q tuples (off_q = its window's offset into the entries), a tail frame -- and every item's bytes
+// follow the item before it, so one exclusive scan of the item sizes places everything:
+//   list_enc_sizes    a thread per item: its query by binary search over off_q + 2 q (strictly
+//                     ascending, so empty queries need no care); nothing for a query that is not OK on the
+//                     host's side or whose page holds a poisoned entry (the device flag: no host sync)
+//   scan              hipcub exclusive sum, 64-bit, over n_items + 1 sizes
+//   list_enc_offsets  a thread per query: body offset, tuples encoded, the poison flag -- one D2H
+//   list_enc_write    a wave per 64 consecutive items.  Staged: when their bytes fit the wave's LDS
+//                     window each lane assembles its item there, at the byte offset it has in the output
+//                     (the window starts at the output's offset mod 16), and the wave streams the window
+//                     out with 16-B stores between a byte-wise head and tail.  Direct: a lane per item
+//                     straight to global memory, field by field in lockstep, so that a string longer
+//                     than LE_COOP_MIN is written by the whole wave (list_wave_raw / list_wave_esc).
+namespace {
+
+constexpr uint32_t LE_THREADS = 256, LE_WAVES = LE_THREADS / 64;
+constexpr uint32_t LE_WINDOW = 16384;        // bytes of LDS per wave
+constexpr uint32_t LE_COOP_MIN = 256;        // the direct path: a longer string is the wave's work
+
+struct LEnc {
+    const uint2* slots;
+    uint64_t n_slots;
+    const uint64_t* wins;                    // per query {wlo, whi, off}
+    const uint32_t* qpage;
+    const uint64_t* meta;                    // per query: the next page's number, or LIST_ENC_FAILED
+    uint32_t n;
+    uint32_t json;
+    uint64_t n_items;                        // n_slots + 2 n
+};
+
+constexpr uint32_t LE_NONE = 0, LE_TUPLE = 1, LE_HEAD = 2, LE_TAIL = 3;
+struct LEItem {
+    uint32_t kind;
+    bool first;                              // a tuple: the first of its body
+    uint2 e;
+    uint64_t token;
+};
+
+__device__ inline LEItem list_enc_item(const LEnc& A, uint64_t i) {
+    LEItem it{LE_NONE, false, make_uint2(0, 0), 0};
+    if (i >= A.n_items || A.n == 0) return it;
+    uint32_t lo = 0, hi = A.n;                             // base(lo) <= i; base(hi) > i or hi == n
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (A.wins[3ull * mid + 2] + 2ull * mid <= i) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t m = A.meta[lo];
+    if (m == LIST_ENC_FAILED) return it;
+    const uint64_t k = A.wins[3ull * lo + 1] - A.wins[3ull * lo], off = A.wins[3ull * lo + 2];
+    if (k && A.qpage[lo]) return it;                       // toInternal fails over the page: no body
+    const uint64_t local = i - (off + 2ull * lo);
+    if (local == 0) {
+        it.kind = LE_HEAD;
+    } else if (local == k + 1) {
+        it.kind = LE_TAIL;
+        it.token = m;
+    } else if (local <= k && off + local - 1 < A.n_slots) {
+        it.kind = LE_TUPLE;
+        it.first = local == 1;
+        it.e = A.slots[off + local - 1];
+    }
+    return it;
+}
+
+__device__ inline uint32_t dec_digits(uint64_t v) {        // 0: the empty token
+    uint32_t d = 0;
+    while (v) {
+        v /= 10;
+        ++d;
+    }
+    return d;
+}
+__device__ inline uint8_t* put_dec(uint8_t* p, uint64_t v) {
+    const uint32_t d = dec_digits(v);
+    for (uint32_t k = d; k > 0; --k) {
+        p[k - 1] = (uint8_t)('0' + v % 10);
+        v /= 10;
+    }
+    return p + d;
+}
+
+// the RelationTuple message without its own tag and length
+__device__ inline uint64_t list_msg_len(const Sub& key, const Sub& sub) {
+    uint64_t m = flen(subject_len(sub));
+    for (int f = 0; f < 3; ++f) {
+        const uint32_t l = slen_of(key.t[f], key.i[f]);
+        if (l) m += flen(l);
+    }
+    return m;
+}
+
+__device__ inline uint64_t list_enc_size(const Tables& T, const LEItem& it, bool json) {
+    if (it.kind == LE_NONE) return 0;
+    if (it.kind == LE_HEAD) return json ? 20 : 0;          // {"relation_tuples":[
+    if (it.kind == LE_TAIL) {
+        const uint32_t d = dec_digits(it.token);
+        return json ? 23 + d : (d ? flen(d) : 0);          // ],"next_page_token":"..."}
+    }
+    const Sub key = subject_of(T, EDGE_SET | it.e.x), sub = subject_of(T, it.e.y);
+    if (json)
+        return (it.first ? 0 : 1) + 13 + esc_len(key.t[0], key.i[0]) + 10 + esc_len(key.t[1], key.i[1]) + 12 +
+               esc_len(key.t[2], key.i[2]) + subject_json_len(sub);
+    return flen(list_msg_len(key, sub));
+}
+
+__global__ void __launch_bounds__(256) list_enc_sizes(LEnc A, Tables T, uint64_t* __restrict__ sz) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n_items) return;
+    sz[i] = list_enc_size(T, list_enc_item(A, i), A.json != 0);
+}
+
+// res: [0, n] the body offsets, [n + 1, 2 n + 1) the tuples encoded, [2 n + 1, 3 n + 1) the poison flags
+__global__ void __launch_bounds__(256) list_enc_offsets(LEnc A, const uint64_t* __restrict__ pos,
+                                                        uint64_t* __restrict__ res) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q > A.n) return;
+    if (q == A.n) {
+        res[q] = pos[A.n_items];
+        return;
+    }
+    const uint64_t k = A.wins[3ull * q + 1] - A.wins[3ull * q], off = A.wins[3ull * q + 2];
+    const uint32_t poisoned = k && A.qpage[q] ? 1u : 0u;
+    res[q] = pos[off + 2ull * q];
+    res[A.n + 1ull + q] = (A.meta[q] == LIST_ENC_FAILED || poisoned) ? 0 : k;
+    res[2ull * A.n + 1 + q] = poisoned;
+}
+
+// one sequence of put_esc: the bytes esc_at's e stands for, at p
+__device__ inline void put_seq(uint8_t* p, const uint8_t* s, uint32_t c, const Esc& e) {
+    if (e.raw) {
+        for (uint32_t k = 0; k < e.take; ++k) p[k] = s[c + k];
+    } else if (e.emit == 2) {
+        p[0] = '\\';
+        p[1] = e.cp == '\n' ? 'n' : e.cp == '\r' ? 'r' : e.cp == '\t' ? 't' : (uint8_t)e.cp;
+    } else {
+        p[0] = '\\';
+        p[1] = 'u';
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t h = (e.cp >> (12 - 4 * k)) & 15u;
+            p[2 + k] = (uint8_t)(h < 10 ? '0' + h : 'a' + (h - 10));
+        }
+    }
+}
+
+// The whole wave copies s[0, l) to p; returns the end.  Every lane calls it with the same arguments.
+__device__ inline uint8_t* list_wave_raw(uint8_t* p, const uint8_t* s, uint32_t l, uint32_t lane) {
+    for (uint32_t c = lane; c < l; c += 64) p[c] = s[c];
+    return p + l;
+}
+
+// The whole wave writes put_esc's text of s[0, l), without the quotes, to p; returns the end.  A lane
+// per byte, 64 bytes a step.  A byte starts a sequence of esc_at's walk unless it is a continuation
+// byte that a valid multi-byte sequence in front of it consumes; such a sequence starts at a lead byte
+// at most three bytes back with only continuation bytes between, and a lead byte -- never a
+// continuation byte itself -- always starts a sequence.  So every lane can tell locally whether its
+// byte starts one and what esc_at emits for it; a prefix sum over the wave places the sequences, and
+// a run without escapes is a plain 64-byte copy.  Every lane calls it with the same arguments.
+__device__ inline uint8_t* list_wave_esc(uint8_t* p, const uint8_t* s, uint32_t l, uint32_t lane) {
+    for (uint32_t c0 = 0; c0 < l; c0 += 64) {
+        const uint32_t i = c0 + lane;
+        Esc e{0, 0, true, 0};
+        if (i < l) {
+            bool covered = false;
+            if ((s[i] >> 6) == 2) {
+                for (uint32_t k = 1; k <= 3 && k <= i; ++k) {
+                    const uint8_t b = s[i - k];
+                    if (b >= 0xC0) {
+                        covered = esc_at(s, i - k, l).take > k;
+                        break;
+                    }
+                    if ((b >> 6) != 2) break;
+                }
+            }
+            if (!covered) e = esc_at(s, i, l);
+        }
+        uint32_t x = e.emit;
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (e.emit) put_seq(p + (x - e.emit), s, i, e);
+        p += __shfl(x, 63);
+    }
+    return p;
+}
+
+__device__ inline uint8_t* bcast_ptr(const uint8_t* p, int src) {
+    const uint64_t v = (uint64_t)p;
+    const uint32_t lo = __shfl((uint32_t)v, src), hi = __shfl((uint32_t)(v >> 32), src);
+    return (uint8_t*)(((uint64_t)hi << 32) | lo);
+}
+
+// One item's bytes at p.  COOP (the direct path): all 64 lanes of the wave are in the call, each with
+// its own item (or none), and walk the six string fields of a tuple in lockstep -- row namespace,
+// object, relation, then the subject's one or three -- each lane writing the literal in front of its
+// field and the field itself when it is short, the wave together every field longer than LE_COOP_MIN.
+template <bool COOP>
+__device__ __forceinline__ void list_enc_put(const Tables& T, const LEItem& it, bool json, uint8_t* p, uint32_t lane) {
+    if (it.kind == LE_HEAD) {
+        if (json) PUT_LIT(p, "{\"relation_tuples\":[");
+    } else if (it.kind == LE_TAIL) {
+        if (json) {
+            p = PUT_LIT(p, "],\"next_page_token\":\"");
+            p = put_dec(p, it.token);
+            PUT_LIT(p, "\"}");
+        } else if (it.token) {
+            *p++ = 0x12;
+            *p++ = (uint8_t)dec_digits(it.token);           // at most 20 digits: one length byte
+            put_dec(p, it.token);
+        }
+    }
+    const bool tup = it.kind == LE_TUPLE;
+    Sub key, sub;
+    key.set = sub.set = false;
+    if (tup) {
+        key = subject_of(T, EDGE_SET | it.e.x);
+        sub = subject_of(T, it.e.y);
+        if (!json) {
+            *p++ = 0x0A;
+            p = put_varint(p, list_msg_len(key, sub));
+        } else if (!it.first) {
+            *p++ = ',';
+        }
+    }
+    const uint8_t tags[3] = {0x0A, 0x12, 0x1A};
+#pragma unroll 1
+    for (int f = 0; f < 6; ++f) {
+        const StrTab* t = nullptr;
+        uint32_t si = NONE_STR, l = 0;
+        bool has = false;                                   // a string is written at this step
+        if (tup && (f < 4 || sub.set)) {
+            const Sub& from = f < 3 ? key : sub;
+            t = from.t[f % 3];
+            si = from.i[f % 3];
+            l = slen_of(t, si);
+            if (json) {
+                has = true;
+                switch (f) {
+                    case 0: p = PUT_LIT(p, "{\"namespace\":"); break;
+                    case 1: p = PUT_LIT(p, ",\"object\":"); break;
+                    case 2: p = PUT_LIT(p, ",\"relation\":"); break;
+                    case 3:
+                        p = sub.set ? PUT_LIT(p, ",\"subject_set\":{\"namespace\":") : PUT_LIT(p, ",\"subject_id\":");
+                        break;
+                    case 4: p = PUT_LIT(p, ",\"object\":"); break;
+                    default: p = PUT_LIT(p, ",\"relation\":"); break;
+                }
+            } else {
+                if (f == 3) {
+                    *p++ = 0x22;
+                    p = put_varint(p, subject_len(sub));
+                    if (sub.set) {
+                        uint64_t in = 0;
+                        for (int g = 0; g < 3; ++g) {
+                            const uint32_t gl = slen_of(sub.t[g], sub.i[g]);
+                            if (gl) in += flen(gl);
+                        }
+                        *p++ = 0x12;
+                        p = put_varint(p, in);
+                    }
+                }
+                has = l != 0 || (f == 3 && !sub.set);       // empty strings are omitted, but for the id
+            }
+        }
+        const bool coop = COOP && has && l > LE_COOP_MIN;
+        if (has && !coop) p = json ? put_esc(p, t, si) : put_str(p, tags[f % 3], t, si);
+        if constexpr (COOP) {
+            const uint8_t* s = nullptr;
+            if (coop) {
+                s = t->bytes + t->off[si];
+                if (json) {
+                    *p++ = '"';
+                } else {
+                    *p++ = tags[f % 3];
+                    p = put_varint(p, l);
+                }
+            }
+            uint64_t mask = __ballot(coop);
+            while (mask) {
+                const int src = __ffsll((unsigned long long)mask) - 1;
+                mask &= mask - 1;
+                const uint8_t* cs = bcast_ptr(s, src);
+                uint8_t* cp = bcast_ptr(p, src);
+                const uint32_t cl = __shfl(l, src);
+                uint8_t* end = json ? list_wave_esc(cp, cs, cl, lane) : list_wave_raw(cp, cs, cl, lane);
+                if ((int)lane == src) p = end;
+            }
+            if (coop && json) *p++ = '"';
+        }
+    }
+    if (tup && json) {
+        if (sub.set) *p++ = '}';
+        *p++ = '}';
+    }
+}
+
+__global__ void __launch_bounds__(LE_THREADS)
+list_enc_write(LEnc A, Tables T, const uint64_t* __restrict__ pos, uint8_t* __restrict__ out, uint32_t use_lds) {
+    // LE_WAVES windows when use_lds, nothing otherwise (the direct path's occupancy is not bound by LDS)
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint64_t i0 = ((uint64_t)blockIdx.x * LE_WAVES + wave) * 64, i = i0 + lane;
+    const bool json = A.json != 0;
+    const bool live = i0 < A.n_items;                       // the same for the whole wave
+    uint64_t b0 = 0, b1 = 0;
+    if (live) {
+        b0 = pos[i0];
+        b1 = pos[min(i0 + 64, A.n_items)];
+    }
+    const uint32_t a = (uint32_t)(b0 & 15u);                // the window starts at the output's offset mod 16
+    const bool staged = live && use_lds && b1 > b0 && a + (b1 - b0) <= LE_WINDOW;
+    const LEItem it = live ? list_enc_item(A, i) : LEItem{LE_NONE, false, make_uint2(0, 0), 0};
+    uint8_t* const w = lds + wave * LE_WINDOW;
+    if (staged) {
+        if (it.kind != LE_NONE) list_enc_put<false>(T, it, json, w + a + (uint32_t)(pos[i] - b0), lane);
+    } else if (live && b1 > b0) {
+        list_enc_put<true>(T, it, json, out + (it.kind != LE_NONE ? pos[i] : b0), lane);
+    }
+    __syncthreads();
+    if (staged) {
+        const uint32_t len = (uint32_t)(b1 - b0);
+        uint8_t* const g = out + b0;
+        const uint32_t head = min(len, (16u - a) & 15u), nvec = (len - head) / 16, tail = head + nvec * 16;
+        if (lane < head) g[lane] = w[a + lane];
+        for (uint32_t v = lane; v < nvec; v += 64)
+            *reinterpret_cast<uint4*>(g + head + 16 * v) = *reinterpret_cast<const uint4*>(w + a + head + 16 * v);
+        if (tail + lane < len) g[tail + lane] = w[a + tail + lane];
+    }
+}
+
+struct ListEncEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ListEncEvents() {
+        HIP_OK(hipEventCreate(&a));
+        if (hipEventCreate(&b) != hipSuccess) {
+            (void)hipEventDestroy(a);
+            throw Error{KETO_E_HIP, "hipEventCreate"};
+        }
+    }
+    ~ListEncEvents() {
+        (void)hipEventDestroy(a);
+        (void)hipEventDestroy(b);
+    }
+};
+
+}  // namespace
+
+void device_list_encode(Snapshot& S, const ListEncodeIn& in, uint32_t encoding, ListEncoded& out,
+                        std::vector<uint32_t>& qpage) {
+    const DevView dv = device_view(S);
+    HIP_OK(hipSetDevice(dv.device));
+    const hipStream_t st = static_cast<hipStream_t>(in.stream);
+    const uint32_t n = in.n;
+    const uint64_t n_items = in.n_slots + 2ull * n;
+    if (n_items >= (1ull << 31)) throw Error{KETO_E_RANGE, "keto_list_encode_batch: more than 2^31 tuples in one call"};
+    // KETO_LIST_ENC_LDS=0: every wave writes straight to global memory (tests, the A/B of the two paths)
+    const char* env = getenv("KETO_LIST_ENC_LDS");
+    const uint32_t use_lds = env ? (atol(env) != 0 ? 1u : 0u) : 1u;
+    ListEncEvents ev;
+    std::lock_guard<std::mutex> lk(S.mu);
+    const bool current = S.proto && S.proto->version == S.version;
+    ProtoState& P = proto_state(S, dv.device);
+    if (!current) {
+        // the refresh copied on the null stream: the list stream, which does not synchronize with it,
+        // waits for it explicitly
+        if (!P.list_ev) HIP_OK(hipEventCreateWithFlags(&P.list_ev, hipEventDisableTiming));
+        HIP_OK(hipEventRecord(P.list_ev, 0));
+        HIP_OK(hipStreamWaitEvent(st, P.list_ev, 0));
+    }
+    ListEncWork& W = P.list_work;
+    const Tables T{P.strs.view(), P.ns.view(), StrTab{nullptr, nullptr, 0}, P.row_ns, P.row_obj, P.row_rel, P.n_rows,
+                   nullptr, nullptr, nullptr, 0, 0, 0};
+    uint64_t* d_meta = W.meta.get<uint64_t>(n);
+    uint64_t* d_sz = W.sz.get<uint64_t>(n_items + 1);
+    uint64_t* d_pos = W.pos.get<uint64_t>(n_items + 1);
+    uint64_t* d_res = W.res.get<uint64_t>(3ull * n + 1);
+    size_t tb = 0;
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_sz, d_pos, n_items + 1, st));
+    void* d_tmp = W.tmp.get<uint8_t>(tb);
+    const LEnc A{static_cast<const uint2*>(in.d_slots), in.n_slots, in.d_wins, in.d_qpage, d_meta, n,
+                 encoding == KETO_ENC_JSON ? 1u : 0u, n_items};
+    const auto g = [](uint64_t k) { return dim3((unsigned)std::max<uint64_t>(1, (k + 255) / 256)); };
+    HIP_OK(hipEventRecord(ev.a, st));
+    HIP_OK(hipMemcpyAsync(d_meta, in.meta, (uint64_t)n * 8, hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(d_sz + n_items, 0, 8, st));
+    hipLaunchKernelGGL(list_enc_sizes, g(n_items), dim3(256), 0, st, A, T, d_sz);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_sz, d_pos, n_items + 1, st));
+    hipLaunchKernelGGL(list_enc_offsets, g(n + 1ull), dim3(256), 0, st, A, d_pos, d_res);
+    HIP_OK(hipGetLastError());
+    // ---- the one host sync before the write: offsets, tuple counts, poison flags, and with them the total
+    std::vector<uint64_t> res(3ull * n + 1);
+    HIP_OK(hipMemcpyAsync(res.data(), d_res, res.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    out.offsets.assign(res.begin(), res.begin() + n + 1);
+    out.tuples.assign(res.begin() + n + 1, res.begin() + 2ull * n + 1);
+    qpage.resize(n);
+    for (uint32_t q = 0; q < n; ++q) qpage[q] = (uint32_t)res[2ull * n + 1 + q];
+    const uint64_t total = res[n];
+    if (total) {
+        out.bytes = static_cast<uint8_t*>(pinned_take(total));   // the caller's from here on
+        out.total = total;
+        uint8_t* d_out = W.out.get<uint8_t>(total + 16);
+        const uint64_t waves = (n_items + 63) / 64;
+        hipLaunchKernelGGL(list_enc_write, dim3((unsigned)((waves + LE_WAVES - 1) / LE_WAVES)), dim3(LE_THREADS),
+                           use_lds ? LE_WAVES * LE_WINDOW : 0, st, A, T, d_pos, d_out, use_lds);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(out.bytes, d_out, total, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipEventRecord(ev.b, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipEventElapsedTime(&out.encode_ms, ev.a, ev.b));
 }
 
 }  // namespace keto
