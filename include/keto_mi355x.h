@@ -911,7 +911,7 @@ int keto_looked_timing(const keto_looked*, float* index_ms, float* candidates_ms
  * This is Expand's answer with Expand's quirks -- one visited map per tree, the depth cut at
  * restDepth <= 1, nil children turned into leaves -- NOT "every subject for which a check is allowed".
  * The two agree when the depth is ample and no subject set is visited twice on different paths; they
- * can differ otherwise.  There is no check-semantics variant.  Per query the call reports what tells
+ * can differ otherwise.  The check-semantics variant is keto_allowed_subjects_batch (below).  Per query the call reports what tells
  * the caller so: `leaves` = the SubjectID leaf nodes of T before deduplication, `set_leaves` = the leaf
  * nodes of T whose subject is a subject set (depth-cut, revisited or empty sets; a node count, not a
  * distinct count).  set_leaves != 0: the list may be cut short by the depth.  Subject-set leaves are
@@ -978,6 +978,93 @@ int keto_subjects_timing(const keto_subjects*, float* expand_ms, float* flatten_
 /* five HIP-event times in ms: the scan and compaction, the wave class, the block class, the radix-sorted
  * class, the counts' copy + windows + emit + the page's DMA (NULL for a NULL result) */
 const float* keto_subjects_stages(const keto_subjects*);
+
+/* ---- Subjects a check allows on an object (repo:keto_amd/csrc/allowed.hip) ----
+ * keto_allowed_subjects_batch answers, per query {namespace_, object, relation, max_depth, page_size,
+ * page}, "who may touch this object" with CHECK semantics: the SubjectIDs S for which keto_check_batch
+ * on namespace_:object#relation@S, at the same request and global max-depth, returns allowed with
+ * KETO_CHECK_OK.  It is the mirror of keto_lookup_objects_batch and the check-semantics counterpart of
+ * keto_subjects_batch (which flattens Expand's tree and carries Expand's quirks instead): the ids come
+ * back as string ids (decode with keto_subject_fields(s, NULL, ...)) in ascending string-id order, for
+ * the reason given in the keto_subjects_batch section (a page token stays meaningful across writes; a
+ * subject first written after the build sorts last); the page is ids [(page-1) * size, page * size)
+ * with page = max(page, 1), page_size 0 = the snapshot's page size; next_page and the total follow the
+ * list rule, the total being the number of allowed subject ids of the whole query.  Subject-set
+ * subjects are NOT returned (the question "which subject sets does a check allow" has no finite
+ * candidate set of stored rows alone; ask keto_check_batch), and there is no partitioned variant.
+ *
+ * Nothing is traversed with the check's quirks twice: a check at clamped depth d says yes only when a
+ * row it enters holds the requested id, and it enters only rows within d - 1 subject-set hops of the
+ * request's row (internal/check/engine.go:54, 88-91).  So the id edges of all rows within d - 1 hops of
+ * the row (namespace_, object, relation), over the stored effective subject-set edges, hold every id
+ * that can be allowed: a superset, gathered by a hop-bounded, level-synchronous BFS over the device
+ * arena for all queries at once (frontier keys deduplicated in a device hash table, so cycles and shared
+ * substructure cost each row once per query).  The distinct candidates are then checked forwards by the
+ * check kernels, each exactly as a keto_check_batch_rows_device request, and the allowed ones compacted
+ * in order: the set returned is exactly the set this engine's check allows, visited-map quirks
+ * included.  Per query, `candidates` = the distinct ids that were checked and `undecided` = of them, the
+ * checks that ended KETO_UNDECIDED; a query with one or more of those is KETO_ALLOWED_UNDECIDED and
+ * returns nothing (ask the reference).  An object or relation string the snapshot has never seen, or a
+ * key with no row, is KETO_ALLOWED_OK with total 0 and candidates 0.  An empty namespace, object or
+ * relation would be a wildcard query, which needs a batch-local row: KETO_ALLOWED_UNSUPPORTED for that
+ * query, the other queries of the batch being answered as usual.
+ *
+ * Errors, as for keto_lookup_objects_batch: NULL arguments are KETO_E_INVALID, checked first; a
+ * host-only snapshot is KETO_E_HIP whatever n is; any part of a partitioned upload (n_parts > 1) is
+ * KETO_E_INVALID; n = 0 gives count 0 and offsets {0}.  More than KETO_ALLOWED_MAX_CANDIDATES
+ * (environment, default 2^28) id edges gathered over the queries of one call fail the call with
+ * KETO_E_INVALID before any check runs; the test is made on an upper bound taken from the rows' headers
+ * (a row walked edge by edge counts every word, its subject sets included, and poisoned edges count), so
+ * a call can be refused with somewhat fewer id edges than the limit, never accepted with more.  Candidates are checked in chunks of KETO_ALLOWED_CHUNK
+ * (environment, default 2^22, at least 64); KETO_ALLOWED_VISITED_SLOTS (environment) sets the initial
+ * size of the BFS's visited table (and the number of keys it is sized for ahead of a level without being
+ * asked, by default 2^16 or four times the keys visited so far); a level that would fill it past half
+ * reports that, the table is sized for the level's set edges and the level runs again, at most once.  The call
+ * holds the snapshot's lock shared from start to end, so candidates, checks and page belong to one
+ * version, and runs one at a time per snapshot on a workspace and stream of its own.  Device memory,
+ * derived, not measured: 8 B per visited (query, row) key and 8 B per slot of the visited table (at
+ * least twice the keys; after a level ran again, twice that level's set edges), 12 B twice per row of a
+ * level (tile count and scan, of two levels), 8 B twice per gathered id edge
+ * (the sort is out of place; the second buffer holds the ranks later), 5 B per distinct candidate (id and
+ * decision), 16 B per candidate of a chunk (its request; the check keeps a translated copy of as many),
+ * 4 B per emitted id; each buffer is kept for the next call up to 256 MB and freed at the end of a call
+ * past that (not counted in keto_snapshot_stats.device_bytes).  The result owns a block of the pinned
+ * pool sized exactly after the totals (a huge page_size allocates nothing) and holds no reference to
+ * the snapshot: it stays readable after keto_snapshot_apply and keto_snapshot_release, until
+ * keto_allowed_free. */
+#define KETO_ALLOWED_OK 0                 /* ids, next_page, total equal per-subject SubjectIsAllowed */
+#define KETO_ALLOWED_UNKNOWN_NAMESPACE 1  /* query namespace unknown: every check is false; no ids, total 0 */
+#define KETO_ALLOWED_UNDECIDED 2          /* >= 1 candidate's check was KETO_UNDECIDED: no ids, total 0; `undecided` says how many */
+#define KETO_ALLOWED_UNSUPPORTED 3        /* empty namespace, object or relation (a wildcard query needs a
+                                             batch-local row): ask keto_check_batch */
+typedef struct {
+    keto_str namespace_, object, relation;  /* all required, taken literally as a check request's are */
+    int32_t  max_depth;                     /* <= 0 or > global -> global, as keto_check_req */
+    uint32_t page_size;                     /* 0 -> the snapshot's page_size */
+    uint32_t page;                          /* 0 = page 1 */
+} keto_allowed_req;
+typedef struct keto_allowed keto_allowed;
+int keto_allowed_subjects_batch(keto_snapshot* s, const keto_allowed_req* reqs, uint32_t n,
+                                int32_t global_max_depth, keto_allowed** out);
+void keto_allowed_free(keto_allowed*);                        /* NULL is fine */
+uint32_t        keto_allowed_count(const keto_allowed*);      /* n */
+const uint32_t* keto_allowed_ids(const keto_allowed*, uint64_t* total_out);  /* string ids (NULL when there are none) */
+const uint64_t* keto_allowed_offsets(const keto_allowed*);    /* n+1; query i = ids[off[i], off[i+1]) */
+const uint8_t*  keto_allowed_status(const keto_allowed*);     /* n x KETO_ALLOWED_* */
+const uint64_t* keto_allowed_next_page(const keto_allowed*);  /* the list rule: 0 on the last page, when there is nothing, or past the end */
+const uint64_t* keto_allowed_totals(const keto_allowed*);     /* allowed subject ids of the whole query */
+const uint64_t* keto_allowed_candidates(const keto_allowed*); /* distinct ids checked for the query */
+const uint64_t* keto_allowed_undecided(const keto_allowed*);  /* of them: checks that ended KETO_UNDECIDED */
+/* of the call that made the result, HIP events on the call's stream: bfs_ms = the seeds and the levels,
+ * dedupe_ms = sort, unique and split, check_ms = the chunks' requests and checks, emit_ms = the rank
+ * scan, the totals, the page and its copy */
+int keto_allowed_timing(const keto_allowed*, float* bfs_ms, float* dedupe_ms, float* check_ms, float* emit_ms);
+/* the BFS of the call that made the result (any pointer may be NULL): the (query, row) keys it visited, the
+ * slots of the visited table at the end, the rows it met that a write had moved (forwarded headers; a level
+ * counted twice counts them twice), the levels it ran, how often the table was enlarged ahead of a level,
+ * and how often a level's emit ran again because the table proved too small for it */
+int keto_allowed_bfs(const keto_allowed*, uint64_t* visited, uint64_t* slots, uint64_t* forwards, uint32_t* levels,
+                     uint32_t* regrows, uint32_t* reruns);
 
 /* The fields of subject references as keto_tree_node.subject holds them, for building expand.Tree
  * values (internal/expand/tree.go:26-30: relationtuple.SubjectID / SubjectSet,

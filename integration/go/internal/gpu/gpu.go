@@ -1104,3 +1104,98 @@ func (s *Snapshot) Subjects(qs []SubjectsQuery, globalMax int) ([]SubjectsResult
 	}
 	return out, nil
 }
+
+// Allowed statuses of AllowedSubjectsBatch (KETO_ALLOWED_*).
+const (
+	AllowedOK               = uint8(C.KETO_ALLOWED_OK)
+	AllowedUnknownNamespace = uint8(C.KETO_ALLOWED_UNKNOWN_NAMESPACE) // every check is false: no ids
+	AllowedUndecided        = uint8(C.KETO_ALLOWED_UNDECIDED)         // a candidate's check exceeded the engine's limits: check the subjects one by one
+	AllowedUnsupported      = uint8(C.KETO_ALLOWED_UNSUPPORTED)       // an empty field (a wildcard query): ask CheckBatch
+)
+
+// AllowedQuery asks which subject ids a check allows on Namespace:Object#Relation (keto_allowed_req).
+// All three fields are required and taken literally.  MaxDepth <= 0 or past the global maximum is the
+// global maximum; PageSize 0 is the snapshot's page size and Page 0 the first page.
+type AllowedQuery struct {
+	Namespace, Object, Relation string
+	MaxDepth                    int
+	PageSize, Page              uint32
+}
+
+// AllowedResult is one query's page of subject ids in ascending string-id order (as SubjectsResult), the
+// next page's number (0: the last page), the count of all allowed subject ids, the distinct ids that
+// were checked and the checks among them that ended undecided.  IDs are set only when Status is AllowedOK.
+type AllowedResult struct {
+	Status     uint8
+	IDs        []string
+	NextPage   uint64
+	Total      uint64
+	Candidates uint64
+	Undecided  uint64
+}
+
+// AllowedSubjectsBatch answers, for many objects, "who may touch this object" with the check's semantics
+// (keto_allowed_subjects_batch): the subject ids S for which check.(*Engine).SubjectIsAllowed on
+// Namespace:Object#Relation@S (internal/check/engine.go:116-123) is true, the visited map's quirks
+// included -- where Subjects gives Expand's flattened tree instead.  Subject sets are not returned.  The
+// ids come back as string ids; their strings are read with keto_subject_fields, one call for the batch.
+// Not for a Partition (KETO_E_INVALID).
+func (s *Snapshot) AllowedSubjectsBatch(qs []AllowedQuery, globalMax int) ([]AllowedResult, error) {
+	n := len(qs)
+	if n == 0 {
+		return nil, nil
+	}
+	var m cmem
+	defer m.free()
+	total := 0
+	for i := range qs {
+		total += len(qs[i].Namespace) + len(qs[i].Object) + len(qs[i].Relation)
+	}
+	m.strings(total)
+	cr := (*C.keto_allowed_req)(m.alloc(n * int(C.sizeof_keto_allowed_req)))
+	cs := unsafe.Slice(cr, n)
+	for i := range qs {
+		q := &qs[i]
+		cs[i] = C.keto_allowed_req{namespace_: m.s(q.Namespace), object: m.s(q.Object), relation: m.s(q.Relation),
+			max_depth: C.int32_t(q.MaxDepth), page_size: C.uint32_t(q.PageSize), page: C.uint32_t(q.Page)}
+	}
+	var r *C.keto_allowed
+	if rc := C.keto_allowed_subjects_batch(s.h, cr, C.uint32_t(n), C.int32_t(globalMax), &r); rc != C.KETO_OK {
+		return nil, lastErr(rc)
+	}
+	defer C.keto_allowed_free(r)
+	var count C.uint64_t
+	ip := C.keto_allowed_ids(r, &count)
+	off := unsafe.Slice(C.keto_allowed_offsets(r), n+1)
+	status := unsafe.Slice(C.keto_allowed_status(r), n)
+	next := unsafe.Slice(C.keto_allowed_next_page(r), n)
+	totals := unsafe.Slice(C.keto_allowed_totals(r), n)
+	cands := unsafe.Slice(C.keto_allowed_candidates(r), n)
+	und := unsafe.Slice(C.keto_allowed_undecided(r), n)
+	var refs []uint32
+	if ip != nil && count > 0 {
+		ids := unsafe.Slice(ip, int(count)) // the result's memory: read before keto_allowed_free
+		refs = make([]uint32, len(ids))
+		for i, id := range ids {
+			refs[i] = uint32(id)
+		}
+	}
+	subjects, err := s.subjects(nil, refs, &m)
+	if err != nil {
+		return nil, err
+	}
+	out := make([]AllowedResult, n)
+	for i := 0; i < n; i++ {
+		out[i] = AllowedResult{Status: uint8(status[i]), NextPage: uint64(next[i]), Total: uint64(totals[i]),
+			Candidates: uint64(cands[i]), Undecided: uint64(und[i])}
+		if out[i].Status != AllowedOK {
+			continue
+		}
+		page := subjects[int(off[i]):int(off[i+1])]
+		out[i].IDs = make([]string, len(page))
+		for k, sub := range page {
+			out[i].IDs[k] = sub.(*relationtuple.SubjectID).ID
+		}
+	}
+	return out, nil
+}

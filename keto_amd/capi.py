@@ -56,11 +56,15 @@ EXPORTS = [
     "keto_subjects_batch", "keto_subjects_batch_ids", "keto_subjects_free", "keto_subjects_count", "keto_subjects_ids",
     "keto_subjects_offsets", "keto_subjects_status", "keto_subjects_next_page", "keto_subjects_totals",
     "keto_subjects_leaves", "keto_subjects_set_leaves", "keto_subjects_timing", "keto_subjects_stages",
+    "keto_allowed_subjects_batch", "keto_allowed_free", "keto_allowed_count", "keto_allowed_ids", "keto_allowed_offsets",
+    "keto_allowed_status", "keto_allowed_next_page", "keto_allowed_totals", "keto_allowed_candidates",
+    "keto_allowed_undecided", "keto_allowed_timing", "keto_allowed_bfs",
 ]
 DELETE_PATH_HOST, DELETE_PATH_DEVICE = 0, 1
 LIST_OK, LIST_NOT_FOUND, LIST_UNDECIDED = 0, 1, 2
 LOOKUP_OK, LOOKUP_UNKNOWN_NAMESPACE, LOOKUP_UNDECIDED, LOOKUP_UNSUPPORTED = 0, 1, 2, 3
 SUBJECTS_OK, SUBJECTS_NOT_FOUND, SUBJECTS_UNDECIDED = 0, 1, 2
+ALLOWED_OK, ALLOWED_UNKNOWN_NAMESPACE, ALLOWED_UNDECIDED, ALLOWED_UNSUPPORTED = 0, 1, 2, 3
 ENC_PROTO, ENC_JSON = 0, 1
 ENCODINGS = {"proto": ENC_PROTO, "json": ENC_JSON}
 PART_SHARED, PART_MIGRATE = 0, 1
@@ -152,6 +156,11 @@ class KLookupReq(C.Structure):
 
 
 class KSubjectsReq(C.Structure):
+    _fields_ = [("namespace_", KStr), ("object", KStr), ("relation", KStr), ("max_depth", C.c_int32),
+                ("page_size", C.c_uint32), ("page", C.c_uint32)]
+
+
+class KAllowedReq(C.Structure):
     _fields_ = [("namespace_", KStr), ("object", KStr), ("relation", KStr), ("max_depth", C.c_int32),
                 ("page_size", C.c_uint32), ("page", C.c_uint32)]
 
@@ -315,6 +324,19 @@ def load():
             f.restype = C.c_void_p
             f.argtypes = [C.c_void_p]
         lib.keto_subjects_timing.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 2
+    if hasattr(lib, "keto_allowed_subjects_batch"):
+        lib.keto_allowed_free.restype = None
+        lib.keto_allowed_free.argtypes = [C.c_void_p]
+        lib.keto_allowed_count.restype = C.c_uint32
+        lib.keto_allowed_count.argtypes = [C.c_void_p]
+        lib.keto_allowed_ids.restype = C.c_void_p
+        lib.keto_allowed_ids.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        for f in (lib.keto_allowed_offsets, lib.keto_allowed_status, lib.keto_allowed_next_page, lib.keto_allowed_totals,
+                  lib.keto_allowed_candidates, lib.keto_allowed_undecided):
+            f.restype = C.c_void_p
+            f.argtypes = [C.c_void_p]
+        lib.keto_allowed_timing.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 4
+        lib.keto_allowed_bfs.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3 + [C.POINTER(C.c_uint32)] * 3
     lib.keto_route_work_bytes.argtypes = [C.c_uint32, C.c_uint32]
     _lib = lib
     return lib
@@ -1142,6 +1164,70 @@ class Snapshot:
         return [(int(r["status"][i]), ids[int(offs[i]):int(offs[i + 1])],
                  str(int(r["next_page"][i])) if r["next_page"][i] else "", int(r["totals"][i]),
                  int(r["leaves"][i]), int(r["set_leaves"][i])) for i in range(len(queries))]
+
+    # ------------------------------------------------------------------ subjects a check allows
+    def _allowed_arrays(self, h):
+        """The arrays of a keto_allowed handle, copied out (the handle stays the caller's)."""
+        n = self.lib.keto_allowed_count(h)
+        total = C.c_uint64()
+        p = self.lib.keto_allowed_ids(h, C.byref(total))
+        get = lambda f, nbytes, dt: np.frombuffer(C.string_at(f(h), nbytes), dtype=dt).copy()
+        out = {"status": get(self.lib.keto_allowed_status, n, np.uint8),
+               "offsets": get(self.lib.keto_allowed_offsets, 8 * (n + 1), np.uint64),
+               "next_page": get(self.lib.keto_allowed_next_page, 8 * n, np.uint64),
+               "totals": get(self.lib.keto_allowed_totals, 8 * n, np.uint64),
+               "candidates": get(self.lib.keto_allowed_candidates, 8 * n, np.uint64),
+               "undecided": get(self.lib.keto_allowed_undecided, 8 * n, np.uint64),
+               "ids": (np.frombuffer(C.string_at(p, 4 * total.value), dtype=np.uint32).copy() if total.value
+                       else np.zeros(0, dtype=np.uint32))}
+        ms = [C.c_float() for _ in range(4)]
+        _check(self.lib.keto_allowed_timing(h, *[C.byref(x) for x in ms]))
+        out["timing"] = tuple(x.value for x in ms)
+        big, small = [C.c_uint64() for _ in range(3)], [C.c_uint32() for _ in range(3)]
+        _check(self.lib.keto_allowed_bfs(h, *[C.byref(x) for x in big + small]))
+        out["bfs"] = dict(zip(("visited", "slots", "forwards", "levels", "regrows", "reruns"), (int(x.value) for x in big + small)))
+        return out
+
+    def allowed_subjects_handle(self, queries, global_max_depth=5):
+        """keto_allowed_subjects_batch -> the keto_allowed handle itself (a c_void_p): read it with
+        _allowed_arrays, give it back with lib.keto_allowed_free.  It outlives writes and the snapshot."""
+        keep = _Keep()
+        n = len(queries)
+        arr = (KAllowedReq * max(1, n))()
+        for k, (ns, obj, rel, depth, size, page) in enumerate(queries):
+            arr[k].namespace_ = keep.s(ns)
+            arr[k].object = keep.s(obj)
+            arr[k].relation = keep.s(rel)
+            arr[k].max_depth = depth
+            arr[k].page_size = size
+            arr[k].page = page
+        h = C.c_void_p()
+        _check(self.lib.keto_allowed_subjects_batch(self.h, arr, C.c_uint32(n), C.c_int32(global_max_depth), C.byref(h)))
+        return h
+
+    def allowed_subjects_raw(self, queries, global_max_depth=5):
+        """keto_allowed_subjects_batch.  queries: (namespace, object, relation, max_depth, page_size, page),
+        page_size 0 = the snapshot's and page 0 = the first -> a dict of arrays copied out of the
+        keto_allowed handle, which is freed here: status[n], offsets[n+1], ids (uint32 string ids,
+        ascending per query), next_page[n], totals[n], candidates[n], undecided[n], timing = (bfs_ms,
+        dedupe_ms, check_ms, emit_ms) and bfs = keto_allowed_bfs's counters as a dict."""
+        h = self.allowed_subjects_handle(queries, global_max_depth)
+        try:
+            assert self.lib.keto_allowed_count(h) == len(queries)
+            return self._allowed_arrays(h)
+        finally:
+            self.lib.keto_allowed_free(h)
+
+    def allowed_subjects(self, queries, global_max_depth=5):
+        """Which subject ids does a check allow on an object: queries as in allowed_subjects_raw -> per
+        query (status, [subject id strings in ascending string-id order], next page token ("" = last
+        page), total allowed subject ids, candidates checked, undecided checks)."""
+        r = self.allowed_subjects_raw(queries, global_max_depth)
+        ids = [f[1] for f in self.subject_fields(r["ids"])] if len(r["ids"]) else []
+        offs = r["offsets"]
+        return [(int(r["status"][i]), ids[int(offs[i]):int(offs[i + 1])],
+                 str(int(r["next_page"][i])) if r["next_page"][i] else "", int(r["totals"][i]),
+                 int(r["candidates"][i]), int(r["undecided"][i])) for i in range(len(queries))]
 
     def subject_fields(self, refs, arena=None):
         """keto_subject_fields: per subject reference ("id", id) or ("set", namespace, object, relation)."""

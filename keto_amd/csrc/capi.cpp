@@ -1598,6 +1598,71 @@ int keto_subjects_timing(const keto_subjects* r, float* expand_ms, float* flatte
 
 const float* keto_subjects_stages(const keto_subjects* r) { return r ? r->r.stage_ms : nullptr; }
 
+// ---- keto_allowed_subjects_batch: the subjects a check allows on an object (allowed.hip)
+struct keto_allowed {
+    AllowedResult r;                        // r.ids: a block of the pinned pool, or NULL
+    ~keto_allowed() { pinned_give(r.ids); }
+};
+
+int keto_allowed_subjects_batch(keto_snapshot* h, const keto_allowed_req* reqs, uint32_t n, int32_t global_max_depth,
+                                keto_allowed** out) {
+    return guarded([&] {
+        if (!h || !out || (n && !reqs)) throw Error{KETO_E_INVALID, "NULL argument"};
+        *out = nullptr;
+        std::shared_lock<RwGate> lk(h->s->rw);        // one version from the candidates to the page
+        auto a = std::make_unique<keto_allowed>();
+        allowed_subjects(*h->s, h->allowed, reqs, n, global_max_depth, a->r);
+        *out = a.release();
+        return KETO_OK;
+    });
+}
+
+void keto_allowed_free(keto_allowed* a) { delete a; }
+
+uint32_t keto_allowed_count(const keto_allowed* a) { return a ? (uint32_t)a->r.status.size() : 0; }
+
+const uint32_t* keto_allowed_ids(const keto_allowed* a, uint64_t* total_out) {
+    if (total_out) *total_out = a ? a->r.offsets.back() : 0;
+    return a ? a->r.ids : nullptr;
+}
+
+const uint64_t* keto_allowed_offsets(const keto_allowed* a) { return a ? a->r.offsets.data() : nullptr; }
+
+const uint8_t* keto_allowed_status(const keto_allowed* a) { return a ? a->r.status.data() : nullptr; }
+
+const uint64_t* keto_allowed_next_page(const keto_allowed* a) { return a ? a->r.next_page.data() : nullptr; }
+
+const uint64_t* keto_allowed_totals(const keto_allowed* a) { return a ? a->r.totals.data() : nullptr; }
+
+const uint64_t* keto_allowed_candidates(const keto_allowed* a) { return a ? a->r.candidates.data() : nullptr; }
+
+const uint64_t* keto_allowed_undecided(const keto_allowed* a) { return a ? a->r.undecided.data() : nullptr; }
+
+int keto_allowed_timing(const keto_allowed* a, float* bfs_ms, float* dedupe_ms, float* check_ms, float* emit_ms) {
+    return guarded([&] {
+        if (!a) throw Error{KETO_E_INVALID, "NULL argument"};
+        if (bfs_ms) *bfs_ms = a->r.bfs_ms;
+        if (dedupe_ms) *dedupe_ms = a->r.dedupe_ms;
+        if (check_ms) *check_ms = a->r.check_ms;
+        if (emit_ms) *emit_ms = a->r.emit_ms;
+        return KETO_OK;
+    });
+}
+
+int keto_allowed_bfs(const keto_allowed* a, uint64_t* visited, uint64_t* slots, uint64_t* forwards, uint32_t* levels,
+                     uint32_t* regrows, uint32_t* reruns) {
+    return guarded([&] {
+        if (!a) throw Error{KETO_E_INVALID, "NULL argument"};
+        if (visited) *visited = a->r.visited;
+        if (slots) *slots = a->r.slots;
+        if (forwards) *forwards = a->r.forwards;
+        if (levels) *levels = a->r.levels;
+        if (regrows) *regrows = a->r.regrows;
+        if (reruns) *reruns = a->r.reruns;
+        return KETO_OK;
+    });
+}
+
 int keto_list_index_info(const keto_snapshot* h, keto_list_index_info_t* out) {
     return guarded([&] {
         if (!h || !out) throw Error{KETO_E_INVALID, "NULL argument"};

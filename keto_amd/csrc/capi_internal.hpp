@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "allowed.hpp"
 #include "list.hpp"
 #include "snapshot.hpp"
 #include "subjects.hpp"
@@ -21,6 +22,9 @@ struct keto_snapshot {
     // keto_subjects_batch: the flatten's device workspace and stream (subjects.hip), freed with the
     // handle, before s and its device state
     mutable keto::SubjectsCache subjects;
+    // keto_allowed_subjects_batch: the BFS's device workspace and stream (allowed.hip), freed with the
+    // handle, before s and its device state
+    mutable keto::AllowedCache allowed;
 };
 
 struct keto_tree_arena {

@@ -1450,6 +1450,7 @@ void list_encode_batch(Snapshot& S, ListCache& C, const keto_list_req* reqs, uin
         throw Error{KETO_E_INVALID, "keto_list_encode_batch: a part of a partitioned snapshot holds only some rows"};
     const DevView V = device_view(S);                        // KETO_E_HIP on a host-only snapshot
     list_begin(S, n, out.r);
+    out.offsets.assign((uint64_t)n + 1, 0);                  // n = 0: offsets {0}, not an empty vector's NULL
     out.tuples.assign(n, 0);
     out.bytes = nullptr;
     out.total = 0;
